@@ -10,10 +10,21 @@ default_rng(42).random exactly as benchmarks/benchmark.py:223-233.
 
 `value` = folds of the whole job / max-over-ranks time.  The timed path (`--path sweep`,
 default) is fit() deferred + a batched call whose folds partition the rows: ONE sweep of the
-Gram kernel yields the full-data matrices and every fold's matrices; the
-eager two-stage path (fit kernel, then fold update) is timed next to it (two_stage_*,
-fit_ms, fold_stage_ms), and so are the reference's one-call-per-fold loop and the
-reference's whole benchmark protocol from host arrays.
+Gram kernel yields the full-data matrices and every fold's matrices.
+
+A plain run sets up, warms up, times `--steps` steps and prints the line; nothing else.
+`--full` adds everything measured or checked beside the headline: the eager two-stage path
+(two_stage_*, fit_ms, fold_stage_ms), the reference's one-call-per-fold loop and its whole
+benchmark protocol from host arrays, the other output policy and the API defaults, the
+per-rank breakdown and the pipelined figure, the in-run parity gate, roofline traffic
+re-measured under rocprofv3, the supplementary HBM-regime shapes, the other BASELINE
+workloads and the CPU baseline.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned in its
+last step (XTX, XTY and the statistics the flags ask for) as DIR/<name>.npy in the
+workload's dtype: whole arrays while they fit in 60 MB in all, otherwise a fixed, seeded
+sample of the larger ones (flattened).  The inputs are seeded, so two builds can be compared
+output for output.
 
 Multi-GPU (launched by torch.distributed.run, one rank per GPU):
   --scaling strong (default)  BASELINE.json's metric: the SAME N x K x M problem and the
@@ -264,6 +275,36 @@ def clock_probe_summary(stamps):
             "cu_time_used": round(float(dq.sum() / (len(s) * span)), 4)}
 
 
+DUMP_BYTES = 60 * 10**6     # all files of one --dump-outputs together (headers aside)
+
+
+def dump_outputs(torch, out, directory, suffix="", budget=DUMP_BYTES):
+    """Write one step's result ((XTX, XTY), (muX, sdX, muY, sdY)) as <directory>/<name><suffix>.npy.
+    The arrays are taken smallest first, each whole if it fits in an equal share of what is left of
+    ``budget``, else a sample of that share: the elements at sorted flat indices drawn from a generator
+    seeded with the array's name, gathered on the device (the same shape gives the same indices)."""
+    import zlib
+
+    (xtx, xty), stats = out
+    named = [(n, t) for n, t in zip(("XTX", "XTY", "mean_X", "std_X", "mean_Y", "std_Y"), (xtx, xty, *stats))
+             if t is not None]
+    named = [(n, t if torch.is_tensor(t) else torch.from_numpy(np.asarray(t))) for n, t in named]
+    named.sort(key=lambda nt: nt[1].numel())
+    os.makedirs(directory, exist_ok=True)
+    left = budget
+    for i, (name, t) in enumerate(named):
+        share = left // (len(named) - i)
+        es_ = t.element_size()
+        if t.numel() * es_ <= share:
+            a = t.detach().cpu().numpy()
+        else:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.unique(rng.integers(0, t.numel(), size=share // es_, dtype=np.int64))
+            a = t.detach().reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
+        left -= a.nbytes
+
+
 def self_launch(n_ranks):
     """Start `torch.distributed.run` with one rank per GPU as a child process, on a free port of the
     loopback interface; the ranks re-enter this script with WORLD_SIZE set.  Returns the child's exit
@@ -296,8 +337,9 @@ def main():
                     help="timed path: lazy fit + one sweep (default) or eager fit + fold update")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="run only warmup + the timed steps (no split timers, two-stage, per-fold-call, "
-                         "supplementary or CPU legs): the command profiled under "
+                    help="with --full: run only warmup + the timed steps and the reference digests (no split "
+                         "timers, two-stage, per-fold-call, supplementary or CPU legs); without --full it changes "
+                         "nothing: a plain run is already headline-only.  The command profiled under "
                          "rocprofv3 for profiles/, so that every launch in the trace is a "
                          "launch of the timed region")
     ap.add_argument("--fresh-outputs", action="store_true",
@@ -306,8 +348,9 @@ def main():
                          "what a loop that consumes each step's results before the next wants; the per-rank step "
                          "of an 8-GPU job is shorter than those allocations)")
     ap.add_argument("--brief", action="store_true",
-                    help="--headline-only plus the full-size from-scratch parity check: what the default N=1 run "
-                         "starts as a child process for every other BASELINE workload (other_workloads)")
+                    help="--headline-only plus the parity gate (with the full-size from-scratch check), with or "
+                         "without --full: what the --full N=1 run starts as a child process for every other "
+                         "BASELINE workload (other_workloads)")
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the child runs of the other BASELINE workloads (C2, C4, C5) at N=1")
     ap.add_argument("--rows", type=int, default=0, help="override the global N (debug / tests)")
@@ -327,11 +370,19 @@ def main():
                          "(one model per stream, the same inputs), so that a step's finalize/exchange overlaps "
                          "the next step's sweep; 1 = skip")
     ap.add_argument("--with-breakdown", action="store_true",
-                    help="with --headline-only: still run the per-rank breakdown and the pipelined figure")
+                    help="with --headline-only or without --full: still run the per-rank breakdown and the "
+                         "pipelined figure")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not re-measure roofline.traffic with rocprofv3 child runs (two short passes, "
                          "~1 min); the figure of profiles/hbm_traffic.json is reported instead")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg, check and figure (see the module docstring); "
+                         "without it a run does only the set-up, the warm-up and the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed path's results of its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python3 bench.py --gpus N` (N > 1) without a launcher: start the ranks ourselves, the way the reference's
     # harness is one command (benchmarks/benchmark.py:293-308).  This process never touches the GPU -- torch is
@@ -509,6 +560,9 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and out is not None:
+        # (several ranks: each writes the folds it computed, under names of its own)
+        dump_outputs(torch, out, args.dump_outputs, f"_rank{rank}" if world > 1 else "", DUMP_BYTES // world)
 
     # ---- per-rank breakdown of a step (outside the timed region) -----------------------------
     # Isolated steps (device idle before each): events on the step's stream at its start, around the
@@ -642,7 +696,7 @@ def main():
             ms = float(tt.item())
         return ms
 
-    ho = args.headline_only or args.brief
+    ho = args.headline_only or args.brief or not args.full
     if emu:
         # ---- one emulated rank: breakdown, pipelined figure, parity of THIS rank's folds, one line ----
         bd = breakdown(timed_model, batch)
@@ -785,9 +839,9 @@ def main():
     # ---- parity gate in the same run ---------------------------------------------------------
     # C2/C3 (host-generated inputs = the reference benchmark's): this rank's folds against the
     # reference digests (tests/golden/g6_digest.npz); every workload: one fold recomputed from
-    # scratch the naive way at full size (direct_fold_check).
+    # scratch the naive way at full size (direct_fold_check).  Part of --full (and of --brief).
     parity = "not checked"
-    if True:
+    if args.full or args.brief:
         notes, ok = [], True
         results = [r for r in ((out, args.path), (other_out, "two_stage" if args.path == "sweep" else "sweep"))
                    if r[0] is not None]

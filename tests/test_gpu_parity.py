@@ -1309,7 +1309,7 @@ def test_bench_command_two_ranks_strong_scaling(amd, mode, path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, CVM_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     port = 29900 + (os.getpid() % 1000) + {"row_sharded": 0, "replicated": 3}[mode] + (5 if path != "sweep" else 0)
-    common = ["--rows", "4000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--mode", mode,
+    common = ["--rows", "4000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--mode", mode,
               "--path", path]
     two = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
@@ -1331,6 +1331,43 @@ def test_bench_command_two_ranks_strong_scaling(amd, mode, path):
     assert line2["scaling_ceiling_vs_1gpu"] == 2.0 and line1["scaling_ceiling_vs_1gpu"] == 1.0
 
 
+def test_bench_plain_run_dumps_the_timed_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) times exactly --steps steps, prints the headline line without
+    running the parity gate, and --dump-outputs writes what the timed path returned in its last step: every fold's
+    XTX, XTY and statistics, here checked against the oracle on the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--rows", "4000", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(d)], cwd=root, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "folds/s" and line["dtype"] == "f64" and line["parity"] == "not checked"
+    assert line["two_stage_ms_per_step"] is None and line["cpu_baseline"] is None and line["other_workloads"] is None
+    N, K, M, P = 4000, 512, 16, 10
+    X, Y, w = bench.synth(N, K, M, np.float64, 42)
+    o = OracleCVMatrix(True, True, True, True, ddof=1)
+    o.fit(X, Y, w)
+    op = OraclePartitioner(np.arange(N) % P)
+    got = {n: np.load(d / f"{n}.npy") for n in ("XTX", "XTY", "mean_X", "std_X", "mean_Y", "std_Y")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    for i, f in enumerate(op.folds_dict):
+        (rx, ry), rst = o.training_XTX_XTY(op.get_validation_indices(f))
+        assert_normwise(got["XTX"][i], rx, TOL, f"fold {f} XTX")
+        assert_normwise(got["XTY"][i], ry, TOL, f"fold {f} XTY")
+        assert_stats(tuple(got[n][i] for n in ("mean_X", "std_X", "mean_Y", "std_Y")), rst, 1e-10, f"fold {f}")
+
+
 def test_bench_plain_command_starts_its_own_ranks():
     """`python3 bench.py --gpus 2 ...` with NO launcher in front -- the form the driver uses for `--gpus 1` -- starts
     `torch.distributed.run` itself as a child process (the parent never touches the GPU), relays rank 0's one JSON
@@ -1345,7 +1382,7 @@ def test_bench_plain_command_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(CVM_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rows", "4000", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True,
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, cwd=root, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -386,3 +386,36 @@ def test_plain_bench_command_with_several_gpus_launches_its_own_ranks(monkeypatc
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and 1024 < int(cmd[cmd.index("--master-port") + 1]) < 65536
     assert cmd[-5] == os.path.join(root, "bench.py") and cmd[-4:] == ["--gpus", "4", "--steps", "3"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path):
+    """bench.py --dump-outputs: one step's results as <name>.npy in their own dtype -- whole while they fit in the
+    byte budget, else the largest become a sample of their share, the same elements on every run."""
+    import sys
+
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    xtx = torch.rand((10, 300, 300), dtype=torch.float64, generator=g)
+    xty = torch.rand((10, 300, 2), dtype=torch.float64, generator=g)
+    mu = torch.rand((10, 1, 300), dtype=torch.float64, generator=g)
+    out = ((xtx, xty), (mu, None, None, None))
+    bench.dump_outputs(torch, out, str(tmp_path / "whole"))
+    assert sorted(os.listdir(tmp_path / "whole")) == ["XTX.npy", "XTY.npy", "mean_X.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "XTX.npy"), xtx.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "mean_X.npy"), mu.numpy())
+    budget = 200_000
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, out, str(tmp_path / d), budget=budget)
+    a = {n: np.load(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")}
+    b = {n: np.load(tmp_path / "b" / n) for n in os.listdir(tmp_path / "b")}
+    assert sum(v.nbytes for v in a.values()) <= budget
+    assert np.array_equal(a["XTY.npy"], xty.numpy()) and a["XTY.npy"].dtype == np.float64
+    assert a["XTX.npy"].ndim == 1 and 0 < a["XTX.npy"].size < xtx.numel()
+    assert np.isin(a["XTX.npy"], xtx.numpy()).all()
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    bench.dump_outputs(torch, ((xtx.float(), xty.float()), (None,) * 4), str(tmp_path / "f32"), budget=budget)
+    assert np.load(tmp_path / "f32" / "XTX.npy").dtype == np.float32

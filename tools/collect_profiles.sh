@@ -41,7 +41,7 @@ python3 $ROOT/tools/bench_f32_midsize.py > $D/bench_f32_midsize.txt 2>/dev/null
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/pls -- python3 $ROOT/tools/bench_pls.py > $D/bench_pls.txt 2> $O/pls.log
 cp $(ls $O/pls/*/*_kernel_stats.csv | head -1) $D/pls_kernel_stats.csv 2>/dev/null
 cd $ROOT
-python3 bench.py > $O/plain.out 2>&1; grep "^{" $O/plain.out | tail -1 > $D/bench_bench_plain.json
+python3 bench.py --full > $O/plain.out 2>&1; grep "^{" $O/plain.out | tail -1 > $D/bench_bench_plain.json
 python3 tools/bench_foldsizes.py > $D/fold_size_sweep.txt 2>/dev/null
 # mid-size folds (P = 1000) under the counters: mid_tile_kernel behind the statistics pre-pass
 FOLD_PS=1000 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/mid_fetch -- python3 $ROOT/tools/bench_foldsizes.py > /dev/null 2>&1

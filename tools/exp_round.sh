@@ -4,7 +4,7 @@ python tools/bench_foldsizes.py > $out/fold_size_sweep.txt 2>/dev/null; cat $out
 for w in C3 C2 C4 C5; do
   extra=""; [ $w = C3 ] || extra="--steps 5 --warmup 2 --no-cpu-baseline"
   [ $w = C2 ] && extra="--steps 50 --warmup 10 --no-cpu-baseline"
-  timeout 900 python bench.py --workload $w $extra > $out/bench_$w.json 2> $out/bench_$w.err
+  timeout 900 python bench.py --full --workload $w $extra > $out/bench_$w.json 2> $out/bench_$w.err
   python - <<PY
 import json
 try:
