@@ -33,10 +33,7 @@ struct ColArgs {
   char *ws;
 };
 constexpr int COL_THREADS = 256;
-#ifndef CVM_COL_UNROLL
-#define CVM_COL_UNROLL 8
-#endif
-constexpr int COL_UNROLL = CVM_COL_UNROLL;
+constexpr int COL_UNROLL = 8;
 constexpr int Y_ELEMS = 2048;                      // elements of Y staged per chunk
 constexpr int Y_PASSES = Y_ELEMS / COL_THREADS;
 
@@ -214,22 +211,18 @@ inline dim3 colstats_grid(const ColArgs &c, int64_t nb) {
   return dim3((unsigned)((int64_t)c.ywgs + nb * c.splits * c.nxb));
 }
 
-// Units per fold of a statistics-only launch.  Measured (tools/exp_colstats.sh, MI355X): the
+// Units per fold of a statistics-only launch.  Measured (forced units per fold, MI355X): the
 // X workgroups of a launch all start at once (up to about five per CU are resident) and a CU
 // streams at a fixed rate, so the launch lasts as long as the CU with the most workgroups:
 // 250 workgroups of 400 rows 70 us, 260 of 385 rows 89 us (410 MB); past the resident limit the
 // dispatcher balances.  Every unit also costs a statistics vector (written, then read by
 // fold_stats_kernel: about 24 rows' worth) and 0.2 us of fold_stats_kernel's serial sum.
-#ifndef CVM_COL_MIN_ROWS
-#define CVM_COL_MIN_ROWS 32
-#endif
+constexpr int COL_MIN_ROWS = 32;
 inline int64_t colstats_splits(int64_t max_rows, int64_t n_folds, int K, size_t elem, int cu_count) {
-  static const char *force = getenv("CVM_COL_SPLITS");     // experiments
-  if (force) return atol(force) < 1 ? 1 : (atol(force) > 1024 ? 1024 : atol(force));
   const int vec = 16 / (int)elem;
   const int nxb = (K + COL_THREADS * vec - 1) / (COL_THREADS * vec);
   const double cus = (double)cu_count;
-  int64_t cap = (max_rows + CVM_COL_MIN_ROWS - 1) / CVM_COL_MIN_ROWS;
+  int64_t cap = (max_rows + COL_MIN_ROWS - 1) / COL_MIN_ROWS;
   if (cap > 1024) cap = 1024;
   if (cap < 1) cap = 1;
   int64_t best = 1;

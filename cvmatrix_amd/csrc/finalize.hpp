@@ -7,19 +7,10 @@
 // finalize kernels
 // ----------------------------------------------------------------------------------
 // Output matrices are written once and never read again by the library: their 16-byte stores are
-// nontemporal (-DCVM_NT_STORES=0 builds the plain-store variant).  Measured (tools/bench_small.py,
-// same box): leave-one-out K=500 1.71 -> 2.06 M folds/s, K=512 n=8 1.25 -> 1.53 M, K=4096 float32
-// n=16 4.55 -> 5.16 TB/s algorithmic, 3000 folds of 33 rows through the fused epilogue +8 %.
-#ifndef CVM_NT_STORES
-#define CVM_NT_STORES 1
-#endif
-template <typename V> __device__ __forceinline__ void out_store(V *p, V v) {
-#if CVM_NT_STORES
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
+// nontemporal.  Measured against plain stores (tools/bench_small.py, same box): leave-one-out K=500
+// 1.71 -> 2.06 M folds/s, K=512 n=8 1.25 -> 1.53 M, K=4096 float32 n=16 4.55 -> 5.16 TB/s
+// algorithmic, 3000 folds of 33 rows through the fused epilogue +8 %.
+template <typename V> __device__ __forceinline__ void out_store(V *p, V v) { __builtin_nontemporal_store(v, p); }
 
 // the write ceiling of the device with this kind of store (cvm_fill_probe): one 16-byte piece per thread, one
 // workgroup per 4 KiB, in linear order.  (tools/fill_variants.hip: this shape reaches 6.7 TB/s where a
@@ -984,23 +975,14 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_apply_kernel(const FinArgs a)
 // ----------------------------------------------------------------------------------
 // One-sweep path with few folds (<= SWF_MAX), everything in two launches after the Gram kernel:
 //   sweep_stats_kernel   full-data column sums (gstats) AND every fold's statistics
-//   sweep_finish_kernel  full-data G, H AND every fold's training matrices, each partial read once
+//   sweep_finish4_kernel full-data G, H AND every fold's training matrices, each partial read once
 // (fit_apply_kernel + fold_stats_kernel + apply_kernel read the folds' partials twice: 68 MB of the
-// 91 MB they move at C3.)  A fold's raw update U_f = sum_sp partial stays in registers; G = sum_f
-// U_f in fold order -- the very sums fit_apply_kernel and apply_kernel form, so the results are
+// 91 MB they move at C3.)  A fold's raw update U_f = sum_sp partial (float64); G = sum_f U_f in
+// fold order -- the very sums fit_apply_kernel and apply_kernel form, so the results are
 // bit-identical to cvm_sweep_fit + cvm_sweep_folds.
 // ----------------------------------------------------------------------------------
-constexpr int SWF_MAX = 16;    // folds whose updates a thread holds
-#ifndef CVM_SWF_R
-#define CVM_SWF_R 16
-#endif
-constexpr int SWF_R = CVM_SWF_R;      // block rows of sweep_finish_kernel (its columns: 256 bytes)
-constexpr int SWF_T = 16 * SWF_R;     // its threads: one 16-byte piece each
-constexpr int SWF_EPW = SWF_T / SWF_MAX;   // XTY elements per workgroup
-#ifndef CVM_SWF_GROUP
-#define CVM_SWF_GROUP 8
-#endif
-constexpr int SWF_GROUP = CVM_SWF_GROUP;   // output matrices finished per barrier round
+constexpr int SWF_MAX = 16;    // folds of the one-sweep path at most
+constexpr int SWF_R = 16;      // block rows of sweep_finish4_kernel
 
 // thread = (column cl of the block's 16, fold fl): the fold's column sums from its s_diag partials,
 // the full-data sums over the folds through LDS, then the fold's mean / std
@@ -1069,233 +1051,24 @@ template <typename T> __global__ __launch_bounds__(256) void sweep_stats_kernel(
   fold_column_finish<T>(a, fl, isX, cc, sv, qv, gs, gq, swt, divisor, isX ? want_sdX : want_sdY, fs);
 }
 
-// Blocks of SWF_R rows x (256 bytes of) columns over the upper triangle of the K x K matrices (a
-// block is inside one 128 x 128 tile of the partials), then ceil(K M / 256) workgroups for XTY.
-// A thread owns one 16-byte piece: the folds' updates of it in registers, their sum = its piece of
-// G; elements below the diagonal are masked (the partials hold nothing there), every finished
-// matrix is stored as rows a / columns b and, through an LDS transpose, as rows b / columns a.
-// Needs 16-byte aligned rows (K * sizeof(T) % 16 == 0) and P <= SWF_MAX.
-template <typename T> __global__ __launch_bounds__(SWF_T) void sweep_finish_kernel(const FinArgs a, T *Gout, T *Hout) {
-  const Geom &g = a.g;
-  const int K = g.K, M = g.M, P = a.n_seg;
-  const int tid = threadIdx.x;
-  constexpr int VW = 16 / (int)sizeof(T);
-  constexpr int C = 16 * VW;                 // block columns
-  typedef T vld_t __attribute__((ext_vector_type(VW)));
-  const int nrb = (K + SWF_R - 1) / SWF_R, ncb = (K + C - 1) / C;
-  const bool cX = a.flags & CVM_CENTER_X, cY = a.flags & CVM_CENTER_Y;
-  const bool sX = a.flags & CVM_SCALE_X, sY = a.flags & CVM_SCALE_Y;
-  const int x = blockIdx.x;
-  if (x >= nrb * ncb) {
-    // ---- XTY: thread = (element el of the workgroup's 16, fold fl): the fold's update from its
-    // s_diag partials, H = their sum over the folds through LDS, then the fold's own result
-    if (M == 0 || !Hout) return;
-    const int el = tid % SWF_EPW, fl = tid / SWF_EPW;
-    const int e = (x - nrb * ncb) * SWF_EPW + el;
-    const bool evalid = e < K * M, fvalid = fl < P;
-    const int ga = evalid ? e / M : 0, m = evalid ? e - ga * M : 0;
-    const size_t hoff = (g.tile_elems * sizeof(T) + 255) / 256 * 256;
-    __shared__ double uh[SWF_MAX][17];
-    double u = 0;
-    if (fvalid) {
-      const char *pf = a.ws + hoff + ((size_t)ga * g.Mp + m) * sizeof(T) + (size_t)fl * a.splits * g.unit_bytes;
-      for (int p0 = 0; p0 < a.s_diag; p0 += 8) {
-        const int cnt = a.s_diag - p0 < 8 ? a.s_diag - p0 : 8;
-        T t8[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t8[j] = *reinterpret_cast<const T *>(pf + (size_t)(p0 + (j < cnt ? j : 0)) * g.unit_bytes);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) if (j < cnt) u += (double)t8[j];
-      }
-      uh[fl][el] = u;
-    }
-    lds_barrier();
-    double h = 0;
-    for (int f = 0; f < P; ++f) h += uh[f][el];
-    const T hT = (T)h;
-    if (!evalid) return;
-    if (fl == 0) Hout[(size_t)ga * M + m] = hT;
-    if (!a.out_XTY || !fvalid) return;
-    {
-      const double *fs = a.fstats + (size_t)fl * fstat_len(K, M);
-      const double swt = fs[2 * K + 2 * M];
-      double v = (double)hT - u;
-      if (cX || cY) v -= swt * (fs[ga] * fs[2 * K + m]);
-      if (sX && sY) v = v * (fs[K + ga] * fs[2 * K + M + m]);
-      else if (sX) v = v * fs[K + ga];
-      else if (sY) v = v * fs[2 * K + M + m];
-      ((T *)a.out_XTY)[((size_t)(a.seg0 + fl) * K + ga) * M + m] = (T)v;
-    }
-    return;
-  }
-  const int rb = x / ncb, cb = x - rb * ncb;
-  const int a0 = rb * SWF_R, b0 = cb * C;
-  if (b0 + C - 1 < a0) return;               // the whole block is below the diagonal
-  const int lr = tid >> 4, lc = (tid & 15) * VW;
-  const int gr = a0 + lr, gc = b0 + lc;
-  const int ti = a0 / TILE, tj = b0 / TILE;
-  const int nsp = (ti == tj) ? a.s_diag : a.s_off;
-  const size_t off = (size_t)tile_id(ti, tj, g.P) * TILE * TILE + (size_t)(a0 - ti * TILE + lr) * TILE + (b0 - tj * TILE + lc);
-  const char *pp = a.ws + off * sizeof(T);
-  // the folds' statistics of this block: [f][0..15] row means, [16..31] row 1/sd, [32..32+C) column
-  // means, [32+C..32+2C) column 1/sd, [32+2C] sw_T
-  constexpr int SL = 32 + 2 * C + 1;
-  __shared__ double stl[SWF_MAX][SL];
-  __shared__ T tm[SWF_GROUP][SWF_R][C + 1];
-  if (a.out_XTX) {
-    for (int q = tid; q < P * SL; q += SWF_T) {
-      const int f = q / SL, i = q - f * SL;
-      const double *fs = a.fstats + (size_t)f * fstat_len(K, M);
-      double v;
-      if (i < 16) v = (cX && a0 + i < K) ? fs[a0 + i] : 0.0;
-      else if (i < 32) v = (sX && a0 + i - 16 < K) ? fs[K + a0 + i - 16] : 1.0;
-      else if (i < 32 + C) v = (cX && b0 + i - 32 < K) ? fs[b0 + i - 32] : 0.0;
-      else if (i < 32 + 2 * C) v = (sX && b0 + i - 32 - C < K) ? fs[K + b0 + i - 32 - C] : 1.0;
-      else v = fs[2 * K + 2 * M];
-      stl[f][i] = v;
-    }
-  }
-  // the folds' updates of this thread's piece, in split order (up to 8 partials requested at a
-  // time), and their sum in fold order
-  double U[SWF_MAX][VW], gsum[VW];
-#pragma unroll
-  for (int e = 0; e < VW; ++e) gsum[e] = 0;
-  vld_t qv[2][8];
-  auto request = [&](int f, int p0, vld_t (&q)[8]) {
-    const char *pf = pp + (size_t)f * a.splits * g.unit_bytes;
-    const int cnt = nsp - p0 < 8 ? nsp - p0 : 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = *reinterpret_cast<const vld_t *>(pf + (size_t)(p0 + (j < cnt ? j : 0)) * g.unit_bytes);
-  };
-  auto add = [&](int p0, const vld_t (&q)[8], double (&u)[VW]) {
-    const int cnt = nsp - p0 < 8 ? nsp - p0 : 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (j < cnt) {
-#pragma unroll
-        for (int e = 0; e < VW; ++e) u[e] += (double)q[j][e];
-      }
-  };
-  request(0, 0, qv[0]);
-#pragma unroll
-  for (int f = 0; f < SWF_MAX; ++f) {
-#pragma unroll
-    for (int e = 0; e < VW; ++e) U[f][e] = 0;
-    if (f < P) {
-      // (requesting fold f + 1 BEFORE fold f is added was measured slower, 25 -> 49 us: the unrolled
-      //  code with its masked tails grows past the instruction cache; tools/exp_sweepfin.sh)
-      add(0, qv[f & 1], U[f]);
-      for (int p0 = 8; p0 < nsp; p0 += 8) { request(f, p0, qv[f & 1]); add(p0, qv[f & 1], U[f]); }
-      if (f + 1 < P) request(f + 1, 0, qv[(f + 1) & 1]);
-#pragma unroll
-      for (int e = 0; e < VW; ++e) gsum[e] += U[f][e];
-    }
-  }
-  // element (gr, gc + e) is this thread's to finish when it is on or above the diagonal
-  bool ok[VW];
-  const bool all_ok = gr < K && gc + VW <= K && gr <= gc;
-#pragma unroll
-  for (int e = 0; e < VW; ++e) ok[e] = gr < K && gc + e < K && gr <= gc + e;
-  T gT[VW];
-#pragma unroll
-  for (int e = 0; e < VW; ++e) gT[e] = (T)gsum[e];
-  // output matrix o: 0 = G, o >= 1 = fold o - 1.  SWF_GROUP matrices per round: the finished
-  // pieces are stored as rows a / columns b and parked in LDS; after one barrier the images
-  // are stored transposed as rows b0 + c / columns a0 + r (strictly below the diagonal).
-  const int mc = tid / (SWF_R / VW), mr = (tid - mc * (SWF_R / VW)) * VW;
-  const int n_out = a.out_XTX ? P + 1 : 1;
-  lds_barrier();                                   // (stl)
-  for (int o0 = 0; o0 < n_out; o0 += SWF_GROUP) {
-#pragma unroll
-    for (int k = 0; k < SWF_GROUP; ++k) {
-      const int o = o0 + k;
-      if (o < n_out) {
-        T vals[VW];
-        T *out;
-        if (o == 0) {
-#pragma unroll
-          for (int e = 0; e < VW; ++e) vals[e] = gT[e];
-          out = Gout;
-        } else {
-          // (o0 is 0 or a multiple of SWF_GROUP: the fold number is known at compile time in
-          //  each of the unrolled cases below, so U stays in registers)
-          double uf[VW];
-#pragma unroll
-          for (int e = 0; e < VW; ++e) uf[e] = 0;
-#pragma unroll
-          for (int f = 0; f < SWF_MAX; ++f)
-            if (f == o - 1) {
-#pragma unroll
-              for (int e = 0; e < VW; ++e) uf[e] = U[f][e];
-            }
-          const double *st = stl[o - 1];
-          const double swt = st[32 + 2 * C], mur = st[lr], sdr = st[16 + lr];
-#pragma unroll
-          for (int e = 0; e < VW; ++e) {
-            double v = (double)gT[e] - uf[e];
-            if (cX) v -= swt * (mur * st[32 + lc + e]);
-            if (sX) v = v * (sdr * st[32 + C + lc + e]);
-            vals[e] = (T)v;
-          }
-          out = (T *)a.out_XTX + (size_t)(a.seg0 + o - 1) * K * K;
-        }
-        T *dst = out + (size_t)gr * K + gc;
-        if (all_ok) {
-          vld_t vv;
-#pragma unroll
-          for (int e = 0; e < VW; ++e) vv[e] = vals[e];
-          if (o) out_store(reinterpret_cast<vld_t *>(dst), vv); else *reinterpret_cast<vld_t *>(dst) = vv;
-        } else {
-#pragma unroll
-          for (int e = 0; e < VW; ++e) if (ok[e]) dst[e] = vals[e];
-        }
-#pragma unroll
-        for (int e = 0; e < VW; ++e) tm[k][lr][lc + e] = vals[e];
-      }
-    }
-    lds_barrier();
-    const int orow = b0 + mc, ocol = a0 + mr;
-    if (orow < K) {
-#pragma unroll
-      for (int k = 0; k < SWF_GROUP; ++k) {
-        const int o = o0 + k;
-        if (o < n_out) {
-          T *out = o ? (T *)a.out_XTX + (size_t)(a.seg0 + o - 1) * K * K : Gout;
-          T *md = out + (size_t)orow * K + ocol;
-          if (ocol + VW <= K && ocol + VW - 1 < orow) {
-            vld_t vv;
-#pragma unroll
-            for (int e = 0; e < VW; ++e) vv[e] = tm[k][mr + e][mc];
-            if (o) out_store(reinterpret_cast<vld_t *>(md), vv); else *reinterpret_cast<vld_t *>(md) = vv;
-          } else {
-#pragma unroll
-            for (int e = 0; e < VW; ++e) if (ocol + e < K && ocol + e < orow) md[e] = tm[k][mr + e][mc];
-          }
-        }
-      }
-    }
-    lds_barrier();
-  }
-}
-
 // ----------------------------------------------------------------------------------
-// sweep_finish4_kernel (round 6): the same blocks, sums and arithmetic as sweep_finish_kernel, with the folds' partial
-// loads dealt over FOUR groups of 256 threads.  The 256-thread kernel walks its <= 16 folds one after the other --
-// request up to 8 partials of a fold, wait, add, next fold: ten dependent memory round trips per thread at C3, with
-// barely more than one workgroup per CU (272 blocks): 25 us for 84 MB, 3.4 TB/s, latency-bound (profiles/r6/
-// pmc_derived.json).  Here thread (piece, group g) loads the folds f = g, g + 4, ... only (2-3 round trips), leaves
-// each fold's update U_f in LDS as float64 -- exactly the value the other kernel keeps in a register --, and after one
-// barrier every thread forms G = sum_f U_f in fold order from LDS (the same chain: the same bits) and group g finishes
-// and stores the outputs o = g, g + 4, ... (o = 0: the full-data matrix; o >= 1: fold o - 1), four matrices per
-// barrier round through four transposition buffers.  Dynamic LDS: P x 256 pieces x 16 or 32 bytes + the statistics
-// + the buffers (65 KB at C3); the host falls back to sweep_finish_kernel when that does not fit.
+// sweep_finish4_kernel (round 6): blocks of SWF_R rows x PPR 16-byte pieces over the upper triangle of the K x K matrices
+// (a block is inside one 128 x 128 tile of the partials), then ceil(K M / EPW) workgroups for XTY.  The folds' partial
+// loads are dealt over FOUR groups of threads: thread (piece, group g) loads the folds f = g, g + 4, ... only (2-3
+// dependent round trips at C3; round 2's 256-thread kernel walked its <= 16 folds one after the other -- ten round trips
+// per thread, barely more than one workgroup per CU (272 blocks): 25 us for 84 MB, 3.4 TB/s, latency-bound, profiles/r6/
+// pmc_derived.json), leaves each fold's update U_f in LDS as float64, and after one barrier every thread forms G = sum_f
+// U_f in fold order from LDS and group g finishes and stores the outputs o = g, g + 4, ... (o = 0: the full-data matrix;
+// o >= 1: fold o - 1), four matrices per barrier round through four transposition buffers: every finished matrix is
+// stored as rows a / columns b and, through the LDS transpose, as rows b / columns a; elements below the diagonal are
+// masked (the partials hold nothing there).  Needs 16-byte aligned rows (K * sizeof(T) % 16 == 0) and P <= SWF_MAX.
+// Dynamic LDS: P x 16 PPR pieces x 16 or 32 bytes + the statistics + the buffers (at SWF_MAX folds 50 KB float64, 86 KB float32).
 // ----------------------------------------------------------------------------------
-// PPR = 16-byte pieces per block row: 16 (blocks of 16 rows x 256 bytes, 1024 threads, 272 blocks at K = 512) or 8 (16 rows x
-// 128 bytes, 512 threads, 528 blocks: two to four workgroups per CU, so that one's loads overlap another's stores).
+// PPR = 16-byte pieces per block row: 8 (16 rows x 128 bytes, 512 threads, 528 blocks at K = 512: two to four workgroups
+// per CU, so that one's loads overlap another's stores) rather than 16 (blocks of 16 rows x 256 bytes, 1024 threads, 272
+// blocks).
 constexpr int SWF4_FG = 4;
-#ifndef CVM_SWF4_PPR
-#define CVM_SWF4_PPR 8
-#endif
+constexpr int SWF4_PPR = 8;
 template <int PPR> constexpr int swf4_threads() { return 16 * PPR * SWF4_FG; }
 template <int PPR> constexpr int swf4_epw() { return swf4_threads<PPR>() / SWF_MAX; }      // XTY elements per workgroup
 template <typename T, int PPR> constexpr size_t swf4_lds_bytes(int P) {
@@ -1319,7 +1092,8 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
   const bool sX = a.flags & CVM_SCALE_X, sY = a.flags & CVM_SCALE_Y;
   const int x = blockIdx.x;
   if (x >= nrb * ncb) {
-    // ---- XTY: thread = (element el of the workgroup's EPW, fold fl): as in sweep_finish_kernel
+    // ---- XTY: thread = (element el of the workgroup's EPW, fold fl): the fold's update from its s_diag partials,
+    // H = their sum over the folds through LDS, then the fold's own result
     if (M == 0 || !Hout) return;
     const int el = tid % SWF4_EPW, fl = tid / SWF4_EPW;
     const int e = (x - nrb * ncb) * SWF4_EPW + el;
@@ -1395,7 +1169,7 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
   }
   // ---- this group's folds: the update of this thread's piece, in split order (up to 8 partials in flight) -> LDS
   // (the NEXT fold of the group requested before the current one is added -- two folds' loads in flight -- was measured
-  //  SLOWER, 22.7 -> 26.9 us: like the 256-thread kernel's same experiment in round 2, more loads in flight per thread do
+  //  SLOWER, 22.7 -> 26.9 us, as in the 256-thread kernel of round 2, 25 -> 49 us: more loads in flight per thread do
   //  not help a kernel whose CUs' memory pipes are already full)
   for (int f = fg; f < P; f += SWF4_FG) {
     double u[VW];

@@ -664,8 +664,6 @@ int small_fold_impl(const void *X, const void *Y, const void *w, const int64_t *
   a.out_muX = out_muX; a.out_sdX = out_sdX; a.out_muY = out_muY; a.out_sdY = out_sdY;
   a.out_fold = out_fold; a.ddof = ddof; a.resolution = resolution; a.flags = flags;
   a.P64 = (K + ST - 1) / ST; a.nT64 = a.P64 * (a.P64 + 1) / 2;
-  static const int noremap_env = getenv("CVM_SMALL_NOREMAP") ? atoi(getenv("CVM_SMALL_NOREMAP")) : 0;   // (measurements)
-  a.noremap = noremap_env;
   a.inl_n = -1;
   if (flags & CVM_IDX_HOST) {            // one fold, indices on the host: into the kernel arguments
     a.inl_n = (int)(offsets[1] - offsets[0]);
@@ -681,8 +679,6 @@ int small_fold_impl(const void *X, const void *Y, const void *w, const int64_t *
     if (fpb < 1) fpb = 1;
     // (the workgroup keeps the row numbers of its folds in 256 slots: 8 folds of up to 32 rows, 4 of 64, 2 of 128)
     a.rshift = max_rows <= 32 ? 5 : (max_rows <= 64 ? 6 : 7);
-    static const int fpb_env = getenv("CVM_SMALL_FPB") ? atoi(getenv("CVM_SMALL_FPB")) : 0;   // (measurements)
-    if (fpb_env > 0) fpb = fpb_env;
     if (fpb > (256 >> a.rshift)) fpb = 256 >> a.rshift;
     a.nb = (int)nb; a.fpb = fpb;
     // (statistics: one workgroup per fold and block of 256 columns -- a thread that walks 16 columns of 16 rows
@@ -714,8 +710,6 @@ int small_fold_impl(const void *X, const void *Y, const void *w, const int64_t *
         int fpr = (int)((int64_t)panels * nb / (16 * 256));
         if (fpr < 1) fpr = 1;
         if (fpr > 8) fpr = 8;   // (measured flat from 8 to 16, worse at 32: too few workgroups)
-        static const int fpr_env = getenv("CVM_SMALL_FPR") ? atoi(getenv("CVM_SMALL_FPR")) : 0;   // (measurements)
-        if (fpr_env > 0) fpr = fpr_env > SA_FPB ? SA_FPB : fpr_env;
         a.fpb = fpr;
         a.gx = panels; a.gy = (int)((nb + fpr - 1) / fpr);
         const dim3 gd((unsigned)(8 * (((size_t)a.gx * a.gy + 7) / 8)));
@@ -750,15 +744,9 @@ int small_fold_impl(const void *X, const void *Y, const void *w, const int64_t *
             //  LDS-DMA instructions per operand instead of three)
             auto run = [&](auto np_tag) -> int {
               constexpr int NPR = decltype(np_tag)::value;
-              // eight waves per workgroup (four per SIMD) unless CVM_RES_WAVES=4 asks for the first kernel (comparisons)
-              static const bool four_env = getenv("CVM_RES_WAVES") && atoi(getenv("CVM_RES_WAVES")) == 4;
-              constexpr bool has4 = NPR <= 16;                       // (the four-wave kernel's LDS holds blocks of at most 16 rows)
-              const bool four = four_env && has4;
-              constexpr int lds4 = 4 * 7 * (NPR + 4) * 128, lds8 = res8_lds<NPR>();
+              constexpr int lds8 = res8_lds<NPR>();
               static std::atomic<unsigned long long> attr_done{0};   // one bit per device (one per instantiation)
               if (attr_needed(attr_done, dev)) {
-                if constexpr (has4)
-                  HIP_OK(hipFuncSetAttribute((const void *)res_apply_kernel<NPR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
                 HIP_OK(hipFuncSetAttribute((const void *)res8_apply_kernel<NPR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds8));
                 attr_set(attr_done, dev);
               }
@@ -768,9 +756,6 @@ int small_fold_impl(const void *X, const void *Y, const void *w, const int64_t *
               for (int b0 = 0; b0 < nblk_all; b0 += RES_WG) {
                 r.blk0 = b0; r.nblk = nblk_all - b0 < RES_WG ? nblk_all - b0 : RES_WG;
                 const unsigned wgs = (unsigned)(8 * (((size_t)r.nblk * groups + 7) / 8));
-                if constexpr (has4) {
-                  if (four) { hipLaunchKernelGGL((res_apply_kernel<NPR>), dim3(wgs), dim3(256), lds4, st, r); continue; }
-                }
                 hipLaunchKernelGGL((res8_apply_kernel<NPR>), dim3(wgs), dim3(512), lds8, st, r);
               }
               return CVM_OK;
@@ -1233,7 +1218,7 @@ int sweep_folds_impl(const int64_t *offsets, int64_t n_total, int64_t fold0, int
 
 // cvm_sweep_all: cvm_sweep_fit and cvm_sweep_folds in one call.  With few folds (<= SWF_MAX) and
 // 16-byte aligned rows the finalize half is two launches that read every partial once
-// (sweep_stats_kernel, sweep_finish_kernel); otherwise the two calls' own kernels.  Same bits.
+// (sweep_stats_kernel, sweep_finish4_kernel); otherwise the two calls' own kernels.  Same bits.
 template <typename T>
 int sweep_all_impl(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
                    const int64_t *host_offsets, int64_t n_folds, int64_t N, int K, int M, int dtype, unsigned flags,
@@ -1287,32 +1272,23 @@ int sweep_all_impl(const void *X, const void *Y, const void *w, const int64_t *i
   f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
   f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
   hipLaunchKernelGGL((sweep_stats_kernel<T>), dim3((unsigned)((K + M + 15) / 16)), dim3(256), 0, st, f, gstats);
-  constexpr int C = 16 * (16 / (int)sizeof(T));
-  const unsigned xb = (unsigned)(((K + SWF_R - 1) / SWF_R) * ((K + C - 1) / C));
   // (round 6) the folds' partial loads dealt over four groups of threads -- 2-3 dependent round trips per thread instead
-  // of ten, the same sums -- when its LDS (the folds' updates of a block, float64) fits; CVM_SWF4=0: the 256-thread kernel
-  static const bool swf4 = !(getenv("CVM_SWF4") && atoi(getenv("CVM_SWF4")) == 0);
-  constexpr int PPR = CVM_SWF4_PPR;
+  // of ten, the same sums; its LDS (the folds' updates of a block, float64) fits for every n_folds <= SWF_MAX
+  constexpr int PPR = SWF4_PPR;
+  static_assert(swf4_lds_bytes<T, PPR>(SWF_MAX) <= (size_t)150 * 1024, "sweep_finish4_kernel: LDS");
   const size_t lds4 = swf4_lds_bytes<T, PPR>((int)n_folds);
-  if (swf4 && lds4 <= (size_t)150 * 1024) {
-    int dev = 0;
-    HIP_OK(hipGetDevice(&dev));
-    static std::atomic<unsigned long long> attr_done{0};   // one bit per device
-    if (attr_needed(attr_done, dev)) {
-      HIP_OK(hipFuncSetAttribute((const void *)sweep_finish4_kernel<T, PPR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      attr_set(attr_done, dev);
-    }
-    constexpr int C4 = PPR * (16 / (int)sizeof(T));
-    const unsigned xb4 = (unsigned)(((K + SWF_R - 1) / SWF_R) * ((K + C4 - 1) / C4));
-    const unsigned hb4 = (Y && M > 0) ? (unsigned)(((size_t)K * M + swf4_epw<PPR>() - 1) / swf4_epw<PPR>()) : 0u;
-    hipLaunchKernelGGL((sweep_finish4_kernel<T, PPR>), dim3(xb4 + hb4), dim3(swf4_threads<PPR>()), lds4, st, f, (T *)G,
-                       (T *)((Y && M > 0) ? H : nullptr));
-    HIP_OK(hipGetLastError());
-    if (splits_out) *splits_out = (int64_t)p.s_off | ((int64_t)p.s_diag << 20);
-    return CVM_OK;
+  int dev = 0;
+  HIP_OK(hipGetDevice(&dev));
+  static std::atomic<unsigned long long> attr_done{0};   // one bit per device
+  if (attr_needed(attr_done, dev)) {
+    HIP_OK(hipFuncSetAttribute((const void *)sweep_finish4_kernel<T, PPR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    attr_set(attr_done, dev);
   }
-  const unsigned hb = (Y && M > 0) ? (unsigned)(((size_t)K * M + SWF_EPW - 1) / SWF_EPW) : 0u;
-  hipLaunchKernelGGL((sweep_finish_kernel<T>), dim3(xb + hb), dim3(SWF_T), 0, st, f, (T *)G, (T *)((Y && M > 0) ? H : nullptr));
+  constexpr int C = PPR * (16 / (int)sizeof(T));
+  const unsigned xb = (unsigned)(((K + SWF_R - 1) / SWF_R) * ((K + C - 1) / C));
+  const unsigned hb = (Y && M > 0) ? (unsigned)(((size_t)K * M + swf4_epw<PPR>() - 1) / swf4_epw<PPR>()) : 0u;
+  hipLaunchKernelGGL((sweep_finish4_kernel<T, PPR>), dim3(xb + hb), dim3(swf4_threads<PPR>()), lds4, st, f, (T *)G,
+                     (T *)((Y && M > 0) ? H : nullptr));
   HIP_OK(hipGetLastError());
   if (splits_out) *splits_out = (int64_t)p.s_off | ((int64_t)p.s_diag << 20);
   return CVM_OK;

@@ -77,16 +77,9 @@ struct MidArgs {
 #define MID_STAMP(i)
 #endif
 constexpr int MID_THREADS = 256;
-#ifndef CVM_MID_SR
-#define CVM_MID_SR 16            // rows per stage
-#endif
-#ifndef CVM_MID_NBUF
-#define CVM_MID_NBUF 2           // stage buffers
-#endif
-#ifndef CVM_MID_WPE
-#define CVM_MID_WPE 4            // workgroups per CU the registers are cut for
-#endif
-constexpr int MID_SR = CVM_MID_SR, MID_NBUF = CVM_MID_NBUF;
+constexpr int MID_SR = 16;               // rows per stage
+constexpr int MID_NBUF = 2;              // stage buffers
+constexpr int MID_WPE = 4;               // workgroups per CU the registers are cut for
 constexpr int MID_STAGE_ELEMS = MID_SR * 128;      // SR rows x (64 + 64) columns
 template <typename T> constexpr size_t mid_region_bytes() {
   const size_t tile = ((size_t)64 * 65 * sizeof(T) + 15) / 16 * 16, ring = (size_t)MID_NBUF * MID_STAGE_ELEMS * sizeof(T);
@@ -422,7 +415,7 @@ __device__ __forceinline__ void mid_tile_item(const MidArgs &a, const int f, con
 }
 
 template <typename T, bool WEIGHTED>
-__global__ __launch_bounds__(MID_THREADS, CVM_MID_WPE) void mid_tile_kernel(const MidArgs a) {
+__global__ __launch_bounds__(MID_THREADS, MID_WPE) void mid_tile_kernel(const MidArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int bid = blockIdx.x;
   const long long item = (long long)(bid & 7) * a.per_xcd + (bid >> 3);

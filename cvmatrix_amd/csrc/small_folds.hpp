@@ -39,7 +39,6 @@ struct SmallArgs {
   int rshift;                          // small_apply_kernel: 1 << rshift row slots per fold (32, 64, 128); fpb << rshift <= 256
   int gx, gy;                          // small_apply_kernel: tiles + panels, fold groups
   int x0;                              // small_apply_kernel: first tile / panel number of this launch
-  int noremap;                         // 1: workgroup b works on item b (no XCD-contiguous ranges)
 };
 
 template <typename T, bool WEIGHTED> __global__ __launch_bounds__(256) void small_stats_kernel(const SmallArgs a) {
@@ -140,17 +139,15 @@ constexpr int SA_PITCH = 80;            // LDS row pitch of As / Bs in elements 
 constexpr int SA_FPB = 8;               // folds per workgroup at most (host: fpb <= 8)
 // (at least four waves per SIMD: float32 then fits 128 registers -- four workgroups per CU instead of
 //  three -- and gains 3-7 %; float64 is not bound by occupancy)
-#ifndef CVM_SMALL_WPE
-#define CVM_SMALL_WPE 4
-#endif
-template <typename T, bool WEIGHTED> __global__ __launch_bounds__(256, CVM_SMALL_WPE) void small_apply_kernel(const SmallArgs a) {
+constexpr int SMALL_WPE = 4;
+template <typename T, bool WEIGHTED> __global__ __launch_bounds__(256, SMALL_WPE) void small_apply_kernel(const SmallArgs a) {
   // Workgroups go to the 8 XCDs round-robin by their linear number; neighbouring tiles of one
   // output matrix share cache lines when its rows are not whole lines, and only one L2 can merge
   // the two halves before they go to HBM: give every XCD a contiguous range of (fold group, tile).
   // (a 1-D launch of 8 * ceil(gx * gy / 8) workgroups; gx tiles and panels, gy fold groups)
   const unsigned lin = blockIdx.x, tot = (unsigned)a.gx * (unsigned)a.gy;
   const unsigned per = (tot + 7) / 8;
-  const unsigned item = a.noremap ? lin : (lin & 7) * per + (lin >> 3);
+  const unsigned item = (lin & 7) * per + (lin >> 3);
   if (item >= tot) return;
   const int x = a.x0 + (int)(item % (unsigned)a.gx), by = (int)(item / (unsigned)a.gx);
   const int K = a.K, M = a.M;
@@ -415,15 +412,9 @@ template <typename T, bool WEIGHTED> __global__ __launch_bounds__(256, CVM_SMALL
 // validation rows, means, stds) goes straight from global memory to registers.
 // Rows of the output a workgroup takes per fold (the panel): 32 KB of output either way -- 8 rows of float64, 16
 // rows of float32 (round 4, same box: K = 500 float32 one-row folds 1.305 -> 0.990 ms with 16 rows; float64
-// with 16 rows 0.845 -> 1.225 ms, with 4 rows the same as 8; tools/exp_rows_panel.sh).
-#ifndef CVM_SR_ROWS
-#define CVM_SR_ROWS 8
-#endif
-#ifndef CVM_SR_ROWS_F32
-#define CVM_SR_ROWS_F32 16
-#endif
+// with 16 rows 0.845 -> 1.225 ms, with 4 rows the same as 8).
 // (float32 rows of more than 128 pieces -- K > 512 -- keep 8: sixteen passes per thread leave one workgroup per CU)
-template <typename T> constexpr int sr_rows(int lpr) { return (sizeof(T) == 4 && lpr <= 128) ? CVM_SR_ROWS_F32 : CVM_SR_ROWS; }
+template <typename T> constexpr int sr_rows(int lpr) { return (sizeof(T) == 4 && lpr <= 128) ? 16 : 8; }
 // LPR: 16-byte pieces per output row handled by a workgroup (64, 128 or 256: the smallest that
 // covers K keeps the threads busy); 256 / LPR rows go in one pass, SR_ROWS rows per workgroup.
 template <typename T, bool WEIGHTED, int LPR>
@@ -451,7 +442,7 @@ __global__ __launch_bounds__(256) void small_rows_kernel(const SmallArgs a) {
   // XCD-contiguous ranges of (fold group, panel), as in small_apply_kernel
   const unsigned lin = blockIdx.x, tot = (unsigned)a.gx * (unsigned)a.gy;
   const unsigned per = (tot + 7) / 8;
-  const unsigned item = a.noremap ? lin : (lin & 7) * per + (lin >> 3);
+  const unsigned item = (lin & 7) * per + (lin >> 3);
   if (item >= tot) return;
   const int bx = (int)(item % (unsigned)a.gx), by = (int)(item / (unsigned)a.gx);
   const int ncc = (K + TC - 1) / TC;               // column chunks

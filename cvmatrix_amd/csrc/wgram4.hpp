@@ -30,34 +30,17 @@
 // One s_barrier per 16-row stage joins all eight waves.
 // ----------------------------------------------------------------------------------
 constexpr int NT4 = 512;
-// Partial tiles go to the workspace once and are read once, by another kernel: nontemporal stores (experiment
-// CVM_PARTIAL_NT; 0 = plain stores, whose dirty lines wait in the L2s for the end-of-kernel write-back)
-#ifndef CVM_PARTIAL_NT
-#define CVM_PARTIAL_NT 0
-#endif
-template <typename T> __device__ __forceinline__ void partial_store(T *p, T v) {
-#if CVM_PARTIAL_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-#ifndef CVM_INTERLEAVE
-#define CVM_INTERLEAVE 1
-#endif
+// Partial tiles go to the workspace once and are read once, by another kernel: plain stores, whose dirty lines wait in
+// the L2s for the end-of-kernel write-back (nontemporal stores measured the same: Gram +-0.2 %)
+template <typename T> __device__ __forceinline__ void partial_store(T *p, T v) { *p = v; }
 // Shape of a compute wave's block of a plain off-diagonal tile (round 6).  64 x 64 (4 x 4 MFMA tiles: 4 A-side and
 // 4 B-side fragments per k-step) was the shape of rounds 1-5; 32 x 128 (2 x 8: wave w owns rows 32 w .. 32 w + 31 of
 // the tile and all of its columns) reads 10 fragments instead of 8 but WEIGHTS only 2 instead of 4 -- the A side is
 // the weighted one, and every element of the A panel is then multiplied by exactly one wave, the minimum.
 // tools/f32_loop_probe.hip: a vector instruction inside the MFMA stream costs the matrix pipe ~12 cycles in float32
 // (the float32 MFMA runs on the vector unit's own multipliers: the two are one resource), the 16 weighting
-// multiplies of a stage 8 % of the loop; with 8 of them 0.862 -> 0.890 of the peak in the probe.  Per element type:
-#ifndef CVM_WIDE_F32
-#define CVM_WIDE_F32 1
-#endif
-#ifndef CVM_WIDE_F64
-#define CVM_WIDE_F64 1
-#endif
+// multiplies of a stage 8 % of the loop; with 8 of them 0.862 -> 0.890 of the peak in the probe.  Both element types
+// take 32 x 128 (profiles/r6/wide_blocks_ab.txt).
 constexpr int NBUF4 = 4;        // LDS stage buffers
 constexpr size_t LDS4_BYTES = (size_t)NBUF4 * BUF_ELEMS * 8;   // float64; float32 uses half of it
 template <typename T> constexpr size_t lds4_bytes() { return (size_t)NBUF4 * BUF_ELEMS * sizeof(T); }
@@ -352,9 +335,6 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
     //  MFMA stream issue slots -- C3 Gram launch 0.469 ms at loader 3 / compute 0 and at 1 / 0, 0.463 at
     //  3 / 2, 0.452-0.453 at 0 / 0, 0 / 1..3, 1 / 3, 2 / 3; C4 16.89 -> 16.29 ms, C5 28.56 -> 26.96 ms.
     //  Everybody stays at the default priority 0.)
-#ifdef CVM_LOADER_PRIO
-    __builtin_amdgcn_s_setprio(CVM_LOADER_PRIO);
-#endif
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       row_numbers(t, rn, ok);
@@ -489,7 +469,7 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
   // packed adds + the moves that zero / carry the sets, in front of idle matrix cores -- every 256 rows
   // +2.3 % on the Gram launch, every 1024 rows +0.5 %; a fold test INSIDE the stage loop cost 4 % by itself,
   // hence the two nested loops below.
-  constexpr bool TWO_LEVEL = CVM_TWO_LEVEL && sizeof(T) == 4;
+  constexpr bool TWO_LEVEL = sizeof(T) == 4;
   acc_t acc2[TWO_LEVEL ? 16 : 1];
   if (TWO_LEVEL) {
 #pragma unroll
@@ -498,16 +478,13 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
   double st_s[4] = {0, 0, 0, 0}, st_q[4] = {0, 0, 0, 0};
 
   const int lk = lane >> 4, lc = lane & 15;
-  // (the plain off-diagonal wave of the two-stage / sweep routes: a 32 x 128 block, see CVM_WIDE_*)
-  constexpr bool WIDE = !HWR && MFMR && ROLER == 0 && !FUSEDR && (sizeof(T) == 4 ? CVM_WIDE_F32 : CVM_WIDE_F64);
+  // (the plain off-diagonal wave of the two-stage / sweep routes: a 32 x 128 block: see "Shape of a compute wave's block" above)
+  constexpr bool WIDE = !HWR && MFMR && ROLER == 0 && !FUSEDR;
   const int a_col = h_wave ? 0 : (WIDE ? 32 * wave : 64 * wr);
   const int b_col = h_wave ? 0 : (WIDE ? 0 : 64 * wc);
   const int a_off = a_col + lc;
   const int b_off = h_wave ? PANEL_ELEMS + lc : (diag ? 0 : PANEL_ELEMS) + b_col + lc;
 
-#ifdef CVM_COMPUTE_PRIO
-  __builtin_amdgcn_s_setprio(CVM_COMPUTE_PRIO);
-#endif
   __syncthreads();   // B_a
   __syncthreads();   // B_-1: stage 0 is in buffer 0
 
@@ -603,7 +580,7 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
 #endif
     const T *buf = smem + (s % NBUF4) * BUF_ELEMS;
     const T *nbuf = smem + ((s + 1) % NBUF4) * BUF_ELEMS;
-    if constexpr (CVM_INTERLEAVE && MFM && !HW && ROLE == 0) {
+    if constexpr (MFM && !HW && ROLE == 0) {
       // the plain off-diagonal wave (16 MFMAs per k-step, no column sums): ONE other instruction
       // -- an LDS fragment read of the next k-step, then its four weighting multiplies -- right
       // behind each MFMA, the order pinned by a scheduling barrier after every pair.  The wave's
@@ -934,9 +911,6 @@ constexpr DiagTab diag_tab(int W, bool strips) {
   }
   return t;
 }
-#ifndef CVM_DIAG_STRIPS
-#define CVM_DIAG_STRIPS 1
-#endif
 
 template <typename T, bool WEIGHTED, bool GATHER, int W, int NBY, bool YSTAT, bool FUSEDR = false>
 __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int xcd_q, int slot_q) {
@@ -958,14 +932,14 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
   r0 = uni64(r0); r1 = uni64(r1);
   const int nstages = uni((int)((r1 - r0 + STAGE_ROWS - 1) / STAGE_ROWS));
 
-  constexpr DiagTab P = diag_tab(W, CVM_DIAG_STRIPS && NBY == 1);
+  constexpr DiagTab P = diag_tab(W, NBY == 1);
   constexpr int NF = P.nf, NA = P.na, NG = P.ng, NX = P.nx;
   acc_t acc[NG], acch[NX * NBY];
 #pragma unroll
   for (int i = 0; i < NG; ++i) acc[i] = (acc_t){0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < NX * NBY; ++i) acch[i] = (acc_t){0, 0, 0, 0};
-  constexpr bool TWO_LEVEL = CVM_TWO_LEVEL && sizeof(T) == 4;      // float32: two-level sums, see wgram4_body
+  constexpr bool TWO_LEVEL = sizeof(T) == 4;      // float32: two-level sums, see wgram4_body
   acc_t acc2[TWO_LEVEL ? NG : 1], acch2[TWO_LEVEL ? NX * NBY : 1];
   if (TWO_LEVEL) {
 #pragma unroll
@@ -993,9 +967,6 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
     }
     ink_tot[0] = a.gstats[2 * g.K + 2 * g.M]; ink_tot[1] = a.gstats[2 * g.K + 2 * g.M + 1];
   }
-#ifdef CVM_COMPUTE_PRIO
-  __builtin_amdgcn_s_setprio(CVM_COMPUTE_PRIO);
-#endif
   __syncthreads();   // B_a
   __syncthreads();   // B_-1: stage 0 is in buffer 0
 
@@ -1056,7 +1027,6 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
     for (int ks = 0; ks < 4; ++ks) {
       const int c = ks & 1;
       constexpr int NM = NG + NX * NBY;
-#if CVM_INTERLEAVE
       // one LDS read of the next k-step right behind each MFMA, the order pinned (see the
       // off-diagonal wave in wgram4_body): first what the weighting / column sums need (w, the
       // A-side fragments, the Y fragments), then the other fragments (DiagTab::rd); the weighting
@@ -1075,18 +1045,6 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
         if (i == NM - 1) prepare(c ^ 1);
         __builtin_amdgcn_sched_barrier(0);
       }
-#else
-      if (ks < 3) read_frags(buf, ks + 1, c ^ 1); else read_frags(nbuf, 0, c ^ 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < NM / 2; ++i) mfma_i(i, c);
-      __builtin_amdgcn_sched_barrier(0);
-      prepare(c ^ 1);   // the other slot: its LDS reads were issued most of a k-step ago
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = NM / 2; i < NM; ++i) mfma_i(i, c);
-      __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     __syncthreads();   // B_s
   }

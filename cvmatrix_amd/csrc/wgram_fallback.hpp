@@ -151,7 +151,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void wgram_kernel(const WgramArgs<T> a
   acc_t acc[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = (acc_t){0, 0, 0, 0};
-  constexpr bool TWO_LEVEL = CVM_TWO_LEVEL && sizeof(T) == 4;      // float32: two-level sums, see wgram4_body (wgram4.hpp)
+  constexpr bool TWO_LEVEL = sizeof(T) == 4;      // float32: two-level sums, see wgram4_body (wgram4.hpp)
   acc_t acc2[TWO_LEVEL ? 8 : 1];
   if (TWO_LEVEL) {
 #pragma unroll

@@ -1868,7 +1868,7 @@ def _resident_case(amd, K, M, sizes, reps, torch):
 
 
 def test_resident_route_is_the_default_for_wide_float32_batches(amd):
-    """The library's own rule (cvm_debug_resident mode 2): float32, K = 4096, 40 folds of at most 16 rows -> res_apply_kernel
+    """The library's own rule (cvm_debug_resident mode 2): float32, K = 4096, 40 folds of at most 16 rows -> res8_apply_kernel
     (BASELINE's C5-hbm shape).  The default call must be bit-identical to the forced route (same kernel), within the float32 gate
     of the oracle, exactly symmetric, and agree with the tile kernel (mode 0) to float32 rounding."""
     import torch

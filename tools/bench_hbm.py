@@ -53,7 +53,6 @@ def fill():
 
 
 if __name__ == "__main__":
-    print("CVM_SMALL_TILE =", os.environ.get("CVM_SMALL_TILE", "(default)"), " CVM_SMALL_FPB =", os.environ.get("CVM_SMALL_FPB", "-"))
     fill()
     if len(sys.argv) > 1 and sys.argv[1] == "resident":     # the shapes of the round-6 resident route (CVM_RESIDENT=1: wherever the shape allows; 0: never; default: K >= 4096 and >= 32 folds)
         print("CVM_RESIDENT =", os.environ.get("CVM_RESIDENT", "(default)"))

@@ -1,4 +1,4 @@
-# experiment: variants of sweep_finish_kernel (tools/var/lib_*.so), kernel time under rocprofv3
+# experiment: variants of the sweep's finish kernel (tools/var/lib_*.so), kernel time under rocprofv3
 cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 for v in $VARS; do

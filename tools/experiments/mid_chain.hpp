@@ -50,7 +50,7 @@ __device__ __forceinline__ void chain_wait_vmcnt_le(int n) {
 }
 
 template <typename T, bool WEIGHTED>
-__global__ __launch_bounds__(MID_THREADS, CVM_MID_WPE) void mid_chain_kernel(const MidArgs a) {
+__global__ __launch_bounds__(MID_THREADS, MID_WPE) void mid_chain_kernel(const MidArgs a) {
   typedef typename MF<T>::acc_t acc_t;
   constexpr int ES = (int)sizeof(T), EPL = 16 / ES;
   constexpr int SR = 16, KPS = SR / 4;
