@@ -44,6 +44,7 @@ namespace {
 #include "host.hpp"
 #include "partition.hpp"
 #include "pls.hpp"
+#include "ridge.hpp"
 
 }  // namespace
 
@@ -327,6 +328,27 @@ int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const in
     return pls_sse_impl<float>(X, Y, w, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, sse, wsum, ws,
                                ws_bytes, (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_pls_validation_sse: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_ridge_workspace_bytes(int64_t n_folds, int K, int M, int L) {
+  if (n_folds < 0 || K <= 0 || K > RIDGE_MAXK || M <= 0 || M > RIDGE_MAXM || L <= 0 || L > RIDGE_MAXL) return 0;
+  return ridge_workspace_bytes(n_folds, K, M, L);
+}
+
+int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
+                  int dtype, void *B, int32_t *info, void *ws, size_t ws_bytes, void *stream) {
+  if (!XTX || !XTY || !lambdas || !B || !info || !ws) return fail(CVM_EINVAL, "cvm_ridge_fit: null pointer%s");
+  if (n_folds < 0 || K <= 0 || K > RIDGE_MAXK || M <= 0 || M > RIDGE_MAXM)
+    return fail(CVM_EINVAL, "cvm_ridge_fit: bad shape (1 <= K <= 4096, 1 <= M <= 64)%s");
+  if (L <= 0 || L > RIDGE_MAXL) return fail(CVM_EINVAL, "cvm_ridge_fit: 1 <= L <= 256 penalties%s");
+  for (int l = 0; l < L; ++l)
+    if (!(lambdas[l] >= 0.0) || lambdas[l] == HUGE_VAL)
+      return fail(CVM_EINVAL, "cvm_ridge_fit: every penalty must be finite and >= 0%s");
+  if (dtype == CVM_F64)
+    return ridge_fit_impl<double>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
+  if (dtype == CVM_F32)
+    return ridge_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
+  return fail(CVM_EINVAL, "cvm_ridge_fit: dtype must be CVM_F32 or CVM_F64%s");
 }
 
 int cvm_pls_plan(int64_t n_folds, int K, int M, int A, int dtype, int64_t *info) {

@@ -111,10 +111,11 @@ pls_fit_batched.last_status = None
 
 
 def pls_validation_sse(cvm, folds, stats, B: torch.Tensor):
-    """Weighted squared prediction errors of every fold's PLS models on the fold's own validation rows,
+    """Weighted squared prediction errors of every fold's linear models on the fold's own validation rows,
     on the device (``cvm_pls_validation_sse``): ``cvm`` a fitted ``CVMatrix`` with Y, ``folds`` what
     ``training_XTX_XTY_batched`` was given (a ``Partitioner``, index arrays or a ``FoldBatch``), ``stats``
-    the statistics tuple that call returned, ``B`` (F,A,K,M) from ``pls_fit_batched``.  Returns
+    the statistics tuple that call returned, ``B`` any (F,A,K,M) stack of coefficients: ``pls_fit_batched``'s
+    (A components) or ``ridge.ridge_fit_batched(...).B`` (A = the penalties of the grid).  Returns
     ``(sse, wsum)``: float64 tensors (F,A,M) and (F,) -- the cross-validated RMSE with ``a + 1``
     components is ``sqrt(sse.sum(0)[a] / wsum.sum())`` (``cv_rmse``)."""
     if cvm.X is None or cvm.Y is None:

@@ -257,6 +257,27 @@ int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const in
                            int64_t n_folds, int64_t max_fold_rows, int K, int M, int A, int dtype, const void *muX,
                            const void *sdX, const void *muY, const void *sdY, const void *B, double *sse,
                            double *wsum, void *ws, size_t ws_bytes, void *stream);
+/* Ridge regression over a grid of penalties for every fold (no counterpart in the reference; the other
+ * model people fit on the training matrices and tune by cross-validation): for fold f and penalty l
+ *   (XTX[f] + lambdas[l] I) B[f][l] = XTY[f]
+ * by a Cholesky factorisation, one workgroup per (fold, penalty) problem.
+ *   XTX [n_folds][K][K], XTY [n_folds][K][M]   the out_XTX / out_XTY of cvm_fold_update (not modified;
+ *                        XTX is taken as symmetric), 1 <= K <= 4096, 1 <= M <= 64
+ *   lambdas  HOST float64[L], 1 <= L <= 256, each finite and >= 0 (copied into the launch: the caller may
+ *            free it when the call returns)
+ *   B    [n_folds][L][K][M] in `dtype`: the layout cvm_pls_validation_sse scores, penalties in place of
+ *        components
+ *   info int32[n_folds][L]: 0, or j > 0 where the j-th pivot (1-based, as LAPACK potrf) was not finite or
+ *        not > 0: that problem's B is all NaN (never half-written); the other problems are unaffected
+ *   ws   cvm_ridge_workspace_bytes(n_folds, K, M, L) for every problem in flight at once (host arithmetic,
+ *        no device query); any smaller workspace that holds one problem runs fewer problems at a time with
+ *        the same results to the bit.  Less than one problem: CVM_EWORKSPACE.  Bad pointers, shapes,
+ *        penalties or dtype: CVM_EINVAL.  n_folds == 0: nothing is launched.
+ * Arithmetic in float64 for both dtypes (float32 inputs widened on load, B rounded once on store); a
+ * problem's bits depend on its inputs alone, not on the batch around it or on the workspace size. */
+size_t cvm_ridge_workspace_bytes(int64_t n_folds, int K, int M, int L);
+int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
+                  int dtype, void *B, int32_t *info, void *ws, size_t ws_bytes, void *stream);
 /* info[0]=row slices per fold, [1]=rows per slice, [2]=folds per launch, [3]=1 if the slice of XTX
  * stays in LDS, 0 if it is streamed, 2: few folds -- the kernel that keeps the small state of a fold
  * (deflated XTY, P, R) whole in every slice and passes ONE per-fold barrier per component, XTX
