@@ -8,9 +8,10 @@
 //     come out as Z^T with L Z = XTY, so the forward substitution rides along in the same passes;
 //   * the factor lives in the workgroup's workspace slot COLUMN-major (W[k][r] = L[r][k], leading dimension
 //     ld = K + M rounded up to 32), so both MFMA operands of a panel update are 16 consecutive rows of a column;
-//   * panel j (32 columns): (A + lambda I)[r][j..] - L[r][:j] L[j..][:j]^T on v_mfma_f64_16x16x4_f64, lambda
-//     added as the panel is read from XTX; the 32 x 32 diagonal block factored by one wave in registers (lane i
-//     holds row i, fixed order); the rows below it solved against it, one thread per row;
+//   * panel j (32 columns): (A + lambda I)[r][j..] - L[r][:j] L[j..][:j]^T, the products summed from zero on
+//     v_mfma_f64_16x16x4_f64 and taken from A once, lambda added as the panel is read from XTX; the 32 x 32
+//     diagonal block factored by one wave in registers (lane i holds row i, fixed order); the rows below it
+//     solved against it, one thread per row;
 //   * back substitution L^T B = Z by blocks of 32 rows from the bottom: the update by the rows below on MFMA,
 //     cut over the four waves in a fixed interleave and summed in a fixed order, then the 32 x 32 solve.
 // A pivot that is not finite or not > 0 ends the problem: info = its 1-based column, B all NaN (B is written
@@ -70,11 +71,18 @@ __global__ __launch_bounds__(RIDGE_THREADS) void ridge_kernel(const RidgeArgs a)
       const int nbp = K - j0 < RIDGE_NB ? K - j0 : RIDGE_NB;
       // 1. panel: rows [j0, R) x columns [j0, j0 + nbp); wave w takes row blocks of 32 in turn
       for (int r0 = j0 + 32 * wave; r0 < R; r0 += 128) {
-        pls_v4d acc[2][2];
+        // acc = -L[r][:j0] L[j0 + c][:j0]^T, summed from zero and added to A once at the end: a sum that starts
+        // from the entry of A rounds at the size of that entry at every one of its j0 steps, which on a matrix
+        // with a heavy diagonal (a large lambda) costs sqrt(K) roundings where the products themselves are small.
+        // Rows past R hold whatever the slot holds: they feed only output rows that are not stored (ld is a
+        // multiple of 32, so the reads stay inside the column).
+        // (the entries of A are loaded ahead of the loop, so their latency passes under it)
+        pls_v4d acc[2][2], av[2][2];
 #pragma unroll
         for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
-          for (int cj = 0; cj < 2; ++cj)
+          for (int cj = 0; cj < 2; ++cj) {
+            acc[ti][cj] = pls_v4d{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int r = r0 + 16 * ti + sub + 4 * q, c = 16 * cj + col;
@@ -84,10 +92,9 @@ __global__ __launch_bounds__(RIDGE_THREADS) void ridge_kernel(const RidgeArgs a)
                 v = r < K ? (double)X[(size_t)(j0 + c) * K + r] : (double)Y[(size_t)(j0 + c) * M + (r - K)];
                 if (r == j0 + c) v += lam;
               }
-              acc[ti][cj][q] = v;
+              av[ti][cj][q] = v;
             }
-        // acc -= L[r][:j0] L[j0 + c][:j0]^T.  Rows past R hold whatever the slot holds: they feed only
-        // output rows that are not stored (ld is a multiple of 32, so the reads stay inside the column).
+          }
 #pragma unroll 4
         for (int k0 = 0; k0 < j0; k0 += 4) {
           const double *wk = W + (size_t)(k0 + sub) * ld;
@@ -105,7 +112,7 @@ __global__ __launch_bounds__(RIDGE_THREADS) void ridge_kernel(const RidgeArgs a)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int r = r0 + 16 * ti + sub + 4 * q, c = 16 * cj + col;
-              if (c < nbp && r < R) W[(size_t)(j0 + c) * ld + r] = acc[ti][cj][q];
+              if (c < nbp && r < R) W[(size_t)(j0 + c) * ld + r] = av[ti][cj][q] + acc[ti][cj][q];
             }
       }
       __syncthreads();

@@ -24,7 +24,8 @@ WORKSPACE_LIMIT = 4 << 30     # bytes; fewer problems run at once beyond it (sam
 class RidgeFit(NamedTuple):
     """``B`` (F, L, K, M) in the dtype of XTX: ``B[f, l]`` = coefficients of fold f with penalty
     ``lambdas[l]``; ``info`` (F, L) int32 on the device: 0, or j > 0 where pivot j (1-based) was not
-    positive -- ``B[f, l]`` is then NaN."""
+    positive -- ``B[f, l]`` is then NaN.  A NaN in ``XTY`` alone is no failure: ``info`` stays 0,
+    the columns of ``B[f, l]`` whose right-hand side held it are NaN, the other columns are unaffected."""
     B: torch.Tensor
     info: torch.Tensor
 
@@ -78,6 +79,8 @@ def ridge_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, lambdas, *, check: b
         ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         B = torch.empty((F, L, K, M), dtype=XTX.dtype, device=dev)
         info = torch.empty((F, L), dtype=torch.int32, device=dev)
+        if F == 0:                # nothing to launch (and empty tensors have no address to hand over)
+            return RidgeFit(B, info)
         stream = torch.cuda.current_stream(dev).cuda_stream
         rc = lib.cvm_ridge_fit(_lib.ptr(XTX), _lib.ptr(XTY), F, K, M, lam.ctypes.data, L, code, _lib.ptr(B),
                                _lib.ptr(info), _lib.ptr(ws), nbytes, stream)

@@ -268,7 +268,9 @@ int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const in
  *   B    [n_folds][L][K][M] in `dtype`: the layout cvm_pls_validation_sse scores, penalties in place of
  *        components
  *   info int32[n_folds][L]: 0, or j > 0 where the j-th pivot (1-based, as LAPACK potrf) was not finite or
- *        not > 0: that problem's B is all NaN (never half-written); the other problems are unaffected
+ *        not > 0: that problem's B is all NaN (never half-written); the other problems are unaffected.
+ *        A NaN in XTY alone is no failure: info stays 0, the columns of that problem's B whose
+ *        right-hand side held it are NaN, its other columns and the other problems are unaffected
  *   ws   cvm_ridge_workspace_bytes(n_folds, K, M, L) for every problem in flight at once (host arithmetic,
  *        no device query); any smaller workspace that holds one problem runs fewer problems at a time with
  *        the same results to the bit.  Less than one problem: CVM_EWORKSPACE.  Bad pointers, shapes,

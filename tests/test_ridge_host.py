@@ -19,7 +19,7 @@ def lib():
 
 
 def test_workspace_bytes_is_host_arithmetic(lib):
-    for K, M in ((1, 1), (7, 3), (512, 16), (1024, 32), (4096, 1)):
+    for K, M in ((1, 1), (7, 3), (512, 16), (1024, 32), (4096, 1), (100, 64), (257, 33), (4096, 64)):
         one = lib.cvm_ridge_workspace_bytes(1, K, M, 1)
         ld = (K + M + 31) // 32 * 32
         assert one == (K * ld * 8 + 255) // 256 * 256 > 0
