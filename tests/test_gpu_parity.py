@@ -1914,11 +1914,14 @@ def test_resident_route_is_the_default_for_wide_float32_batches(amd):
 
 
 @pytest.mark.parametrize("tool,args,env", [("fuzz_all.py", ["300", "101"], {}), ("fuzz_small.py", ["500", "102"], {}),
-                                           ("fuzz_small.py", ["250", "103"], {"CVM_SMALL_MAXN": "128"})])
+                                           ("fuzz_small.py", ["250", "103"], {"CVM_SMALL_MAXN": "128"}),
+                                           ("fuzz_all.py", ["60", "104"], {"CVM_FUZZ_HARD": "1"}),
+                                           ("fuzz_small.py", ["60", "105"], {"CVM_FUZZ_HARD": "1"})])
 def test_randomised_routes_against_the_oracle(tool, args, env):
     """tools/fuzz_all.py / fuzz_small.py: random shapes, fold structures, element types, flags,
     weights, ddof, lazy or eager fit and call styles through every route of the fold stage,
-    against the oracle (float64 1e-10; float32 twice the oracle's own float32 error + two roundings, cvmatrix_amd/fp32_gate.py)."""
+    against the oracle (float64 1e-10; float32 twice the oracle's own float32 error + two roundings, cvmatrix_amd/fp32_gate.py).
+    CVM_FUZZ_HARD=1: each case with one non-finite or overflowing cell, through the mask-aware comparison of hard_input_cases.py."""
     import subprocess
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

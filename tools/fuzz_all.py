@@ -4,6 +4,8 @@ labels -> the sweep, one call or two; arbitrary ragged subsets with an empty fol
 the fused epilogue, the small-fold kernels), element types, flags, weights with zeros, ddof, lazy or
 eager fit, call styles (batched, the reference's per-fold loop over a Partitioner's arrays, statistics
 only).  float64: 1e-10 norm-wise; float32: twice the oracle's own float32 error + two float32 roundings.
+CVM_FUZZ_HARD=1: every case gets one defect of tests/hard_input_cases.py (a NaN, an Inf, an overflowing cell, in X, Y or
+the weights) and is compared through its mask-aware helper: the oracle's non-finite mask, the same gates on the rest.
   python tools/fuzz_all.py [cases] [seed]"""
 import os, sys
 import numpy as np, torch
@@ -16,6 +18,11 @@ from oracle.cvmatrix_oracle import OracleCVMatrix
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
+HARD = os.environ.get("CVM_FUZZ_HARD") == "1"
+if HARD:
+    import hard_input_cases as hc
+    hrng = np.random.default_rng(rng.integers(1 << 31))
+    np.seterr(all="ignore")        # (a NaN is data here)
 
 
 def nerr(got, ref):
@@ -44,6 +51,9 @@ for c in range(cases):
     flags = tuple(bool(b) for b in rng.integers(0, 2, 4))
     ddof = int(rng.integers(0, 2))
     lazy = bool(rng.integers(0, 2))
+    hard = None
+    if HARD:
+        X, Y, w, hard = hc.random_defect(hrng, X, Y, w, flags)
     if kind == "subsets":
         perm = rng.permutation(N)
         cuts = np.sort(rng.choice(np.arange(1, N), P - 1, replace=False))
@@ -62,7 +72,7 @@ for c in range(cases):
     if o32 is not None:
         o32.fit(X, Y, w)
     style = rng.choice(["batched", "loop", "batched_xtx", "stats"])
-    what = (c, kind, style, N, K, M, len(folds), dt.__name__, flags, ddof, lazy, w is not None)
+    what = (c, kind, style, N, K, M, len(folds), dt.__name__, flags, ddof, lazy, w is not None) + ((hard,) if HARD else ())
     try:
         if style == "stats":
             bst = m.training_statistics_batched(part if part is not None else folds)
@@ -96,7 +106,10 @@ for c in range(cases):
             rst = o.training_statistics(v)
             for a_, b_ in zip(bst, rst):
                 assert (a_ is None) == (b_ is None), what
-                if b_ is not None:
+                if b_ is not None and HARD:
+                    hc.assert_matches_oracle_where_finite(a_[f].double().cpu().numpy(), b_, hc.gate_stats(
+                        1e-10 if dt is np.float64 else 3e-5, 0 if dt is np.float64 else 1e-6), str(what))
+                elif b_ is not None:
                     np.testing.assert_allclose(a_[f].double().cpu().numpy(), b_, rtol=1e-10 if dt is np.float64 else 3e-5,
                                                atol=0 if dt is np.float64 else 1e-6, err_msg=str(what))
             continue
@@ -111,6 +124,15 @@ for c in range(cases):
             else:
                 sx, _ = o32.training_XTX(v)
                 sy = None
+        if HARD:
+            gx = bx[f].double().cpu().numpy()
+            hc.assert_matches_oracle_where_finite(gx, rx, hc.gate_float64() if dt is np.float64 else hc.gate_float32(sx),
+                                                  str((what, "XTX")))
+            if by is not None:
+                hc.assert_matches_oracle_where_finite(by[f].double().cpu().numpy(), ry, hc.gate_float64() if dt is np.float64
+                                                      else hc.gate_float32(sy), str((what, "XTY")))
+            assert hc.symmetric_where_finite(gx), (what, "symmetry")
+            continue
         ex = nerr(bx[f], rx)
         tolx = 1e-10 if dt is np.float64 else fp32_bound(nerr(sx, rx))
         assert ex <= tolx, (what, "XTX", ex, tolx)

@@ -1,6 +1,7 @@
 """Randomised check of the small-fold routes (tile kernel, rows kernel, inline indices, several folds
 per workgroup) against the NumPy oracle: random K (aligned and not), rows per fold, fold counts,
-flags, weights, dtypes.  python tools/fuzz_small.py [cases] [seed]"""
+flags, weights, dtypes.  CVM_FUZZ_HARD=1: every case gets one defect of tests/hard_input_cases.py and is compared through
+its mask-aware helper.  python tools/fuzz_small.py [cases] [seed]"""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,6 +12,12 @@ from oracle.cvmatrix_oracle import OracleCVMatrix
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
 worst = 0.0
+HARD = os.environ.get("CVM_FUZZ_HARD") == "1"
+if HARD:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_input_cases as hc
+    hrng = np.random.default_rng(rng.integers(1 << 31))
+    np.seterr(all="ignore")        # (a NaN is data here)
 for c in range(cases):
     dt = np.float64 if rng.random() < 0.7 else np.float32
     K = int(rng.choice([3, 17, 64, 100, 130, 200, 256, 300, 500, 512, 640, 1000]))
@@ -28,6 +35,8 @@ for c in range(cases):
     if w is not None:
         w[rng.choice(N, N // 9, replace=False)] = 0
     flags = tuple(bool(b) for b in rng.integers(0, 2, 4))
+    if HARD:
+        X, Y, w, hard = hc.random_defect(hrng, X, Y, w, flags)
     perm = rng.permutation(N)
     folds, o = [], 0
     for f in range(P):
@@ -52,6 +61,27 @@ for c in range(cases):
             assert str(e) == str(e2), (str(e), str(e2))
         continue
     tol = 1e-10 if dt is np.float64 else 5e-4
+    if HARD and dt is np.float32:       # (the float32 rule: against the oracle's own float32 run on the same inputs)
+        o32 = OracleCVMatrix(*flags, dtype=np.float32)
+        o32.fit(X, Y, w)
+    for f in (rng.choice(P, min(P, 4), replace=False) if HARD else ()):
+        what = str((c, hard, K, M, nmax, P, flags, dt.__name__, int(f)))
+        sx = sy = None
+        if M:
+            (rx, ry), _ = orc.training_XTX_XTY(folds[f])
+            if dt is np.float32:
+                (sx, sy), _ = o32.training_XTX_XTY(folds[f])
+            hc.assert_matches_oracle_where_finite(by[f].double().cpu().numpy(), ry,
+                                                  hc.gate_float64() if dt is np.float64 else hc.gate_float32(sy), what + " XTY")
+        else:
+            rx, _ = orc.training_XTX(folds[f])
+            if dt is np.float32:
+                sx, _ = o32.training_XTX(folds[f])
+        gx = bx[f].double().cpu().numpy()
+        hc.assert_matches_oracle_where_finite(gx, rx, hc.gate_float64() if dt is np.float64 else hc.gate_float32(sx), what + " XTX")
+        assert hc.symmetric_where_finite(gx), what
+    if HARD:
+        continue        # (per-call against batch compares bits: a NaN is not equal to itself)
     for f in rng.choice(P, min(P, 4), replace=False):
         if M:
             (rx, ry), _ = orc.training_XTX_XTY(folds[f])
