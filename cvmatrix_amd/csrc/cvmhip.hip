@@ -181,6 +181,16 @@ int cvm_debug_stamps3(unsigned long long *host_out) {
   HIP_OK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps3), sizeof(unsigned long long) * 1024 * 8 * 2));
   return CVM_OK;
 }
+int cvm_debug_stamps5(unsigned long long *host_out, int reset) {   // CVM_ITEM_STAMPS x 4 waves x 8 (wgram_fallback.hpp)
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps5), sizeof(unsigned long long) * CVM_ITEM_STAMPS * 4 * 8));
+  if (reset) {
+    void *p = nullptr;
+    HIP_OK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_stamps5)));
+    HIP_OK(hipMemset(p, 0, sizeof(unsigned long long) * CVM_ITEM_STAMPS * 4 * 8));
+  }
+  return CVM_OK;
+}
 int cvm_debug_stamps2(unsigned long long *host_out) {
   HIP_OK(hipDeviceSynchronize());
   HIP_OK(hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamps2), sizeof(unsigned long long) * 1024 * 8 * 4));

@@ -476,6 +476,7 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
     for (int i = 0; i < 16; ++i) acc2[i] = (acc_t){0, 0, 0, 0};
   }
   double st_s[4] = {0, 0, 0, 0}, st_q[4] = {0, 0, 0, 0};
+  int nz_ = 0, ng_ = 0;      // (ROLE 2) weights != 0 / < 0: counted once per stage, see wgram4_diag_body
 
   const int lk = lane >> 4, lc = lane & 15;
   // (the plain off-diagonal wave of the two-stage / sweep routes: a 32 x 128 block: see "Shape of a compute wave's block" above)
@@ -545,8 +546,6 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
           st_s[n] += pv; st_q[n] += (T)(pv * yv);
         }
         st_s[2] += wv[c];
-        st_s[3] += (wv[c] != (T)0) ? 1.0 : 0.0;
-        st_q[3] += (wv[c] < (T)0) ? 1.0 : 0.0;
       }
       if (MFM && WEIGHTED) {
         if (HW) {   // H wave: 2 Y fragments instead of 8 X fragments
@@ -609,6 +608,8 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
         }
       }
     } else if (MFM || ROLE != 0) {
+      T cw = (T)0;
+      if (ROLE == 2) cw = buf[2 * PANEL_ELEMS + lc];   // the stage's sixteen weights, by lane & 15
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const int c = ks & 1;
@@ -632,6 +633,10 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
               if (!TRI || m <= n) acc[m * NB + n] = MF<T>::mfma(af[c][m], bf[c][n], acc[m * NB + n]);
         }
         __builtin_amdgcn_sched_barrier(0);
+      }
+      if (ROLE == 2) {
+        nz_ += __builtin_popcount((unsigned)__builtin_amdgcn_ballot_w64(cw != (T)0) & 0xffffu);
+        ng_ += __builtin_popcount((unsigned)__builtin_amdgcn_ballot_w64(cw < (T)0) & 0xffffu);
       }
     }
 #ifdef CVM_STAMPS
@@ -787,11 +792,11 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
         st[2 * g.Kp + g.Mp + yc * YT + 16 * n + lc] = qv;
       }
     }
-    const double swv = comb(st_s[2]), nzv = comb(st_s[3]), ngv = comb(st_q[3]);
+    const double swv = comb(st_s[2]);
     if (yc == 0 && lane == 0) {
       st[2 * g.Kp + 2 * g.Mp + 0] = swv;
-      st[2 * g.Kp + 2 * g.Mp + 1] = nzv;
-      st[2 * g.Kp + 2 * g.Mp + 2] = ngv;
+      st[2 * g.Kp + 2 * g.Mp + 1] = (double)nz_;
+      st[2 * g.Kp + 2 * g.Mp + 2] = (double)ng_;
     }
   }
   if (h_wave) {
@@ -824,6 +829,13 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
       unsigned long long *o = g_stamps3 + ((size_t)blockIdx.x * 8 + wave) * 2;
       o[0] = c_loop0 - c_entry; o[1] = c_exit - c_loop1;
     }
+    if (lane == 0 && uni(slot_q) < CVM_ITEM_STAMP_STRIDE) {
+      unsigned long long *o = g_stamps5 + ((size_t)(uni(xcd_q) * CVM_ITEM_STAMP_STRIDE + uni(slot_q)) * 4 + wave) * 8;
+      o[0] = c_entry; o[1] = c_loop0 - c_entry; o[2] = c_loop1 - c_loop0; o[3] = t_b; o[4] = t_c;
+      o[5] = (unsigned long long)nstages;
+      o[6] = (unsigned long long)(ti | (tj << 8) | (yc << 16)) | ((unsigned long long)blockIdx.x << 32);
+      o[7] = c_exit;
+    }
   }
 #endif
   ROLE_EXIT();
@@ -845,7 +857,18 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
 //     with one multiply) -- 11 MFMAs each as before, 6 / 8 / 8 / 6 fragment reads.  The same
 //     MFMA sequence per accumulator whoever runs it: the same bits.  (Measured: no faster than
 //     the first, DESIGN.md section 7 -- the fragment reads are not what a diagonal stage waits for.)
-//   YSTAT: this wave also sums the Y columns, sw and nz (wave 3 of panel 0)
+//   YSTAT: the item also forms the Y-side sums (panel 0; the fused route: every panel).  The table shares them
+//     out (ys, ws) to the waves with the least other vector work per k-step, so that no wave of such an item
+//     issues more than four vector instructions per k-step beyond the same wave of an item without them:
+//       one Y tile:  wave 2 (three weighted fragments: 9 vector instructions against 10) sums the Y tile,
+//                    wave 3 the weights;
+//       two Y tiles: every wave issues 8; waves 3 and 2 (5 and 6 fragment reads) sum one Y tile each, wave 1
+//                    the weights.
+//     The non-zero and negative weights are COUNTED, by the wave that sums the weights: once per stage sixteen
+//     lanes read the stage's sixteen weights, one compare each, and the population counts of the two masks go
+//     to scalar integers -- no vector add at all (they used to be two float64 chains of compare, select, add per
+//     k-step on 64 lanes).  Exact integers either way.  Every sum is the chain it always was (lane classes, k
+//     order, comb()): which wave runs it does not enter into it.
 // ----------------------------------------------------------------------------------
 struct DiagTab {
   int nf, na, ng, nx;
@@ -855,6 +878,8 @@ struct DiagTab {
   int xa[3];            // XTY row tiles: A index
   int ca[2];            // column sums of two tiles: A index
   int rd[8];            // the order the fragments of the next k-step are read in: A sides first
+  int ys[2];            // YSTAT items: 1 = this wave sums Y tile n (sum and weighted square sum)
+  int ws;               // YSTAT items: 1 = this wave sums the weights and counts the non-zero / negative ones
 };
 constexpr DiagTab diag_tab_fill(int W, bool strips) {
   DiagTab t{};
@@ -868,8 +893,10 @@ constexpr DiagTab diag_tab_fill(int W, bool strips) {
     for (int j = 0; j < W + 1; ++j) { t.ga[t.nf + j] = 1; t.gb[t.nf + j] = R1 - W + j; }
     t.nx = 2; t.xa[0] = 0; t.xa[1] = 1;
     t.ca[0] = 0; t.ca[1] = 1;
+    t.ys[0] = W == 3; t.ys[1] = W == 2; t.ws = W == 1;
     return t;
   }
+  t.ys[0] = W == 2; t.ws = W == 3;
   if (W == 0 || W == 3) {                 // a 4x4 corner block's upper triangle
     const int b = W == 0 ? 0 : 4;
     t.nf = 4; t.na = 4;
@@ -911,10 +938,18 @@ constexpr DiagTab diag_tab(int W, bool strips) {
   }
   return t;
 }
+// does wave W of a YSTAT item carry any of the Y-side sums?  (the others run the plain instantiation)
+constexpr bool diag_ystat_wave(int W, int NBY) {
+  const DiagTab t = diag_tab(W, NBY == 1);
+  return t.ws || t.ys[0] || (NBY > 1 && t.ys[1]);
+}
 
 template <typename T, bool WEIGHTED, bool GATHER, int W, int NBY, bool YSTAT, bool FUSEDR = false>
 __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int xcd_q, int slot_q) {
   typedef typename MF<T>::acc_t acc_t;
+#ifdef CVM_STAMPS
+  const unsigned long long c_entry = __builtin_amdgcn_s_memtime();
+#endif
   const WgramArgs<T> a = kernel_args<T>(kargs);
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T *smem = reinterpret_cast<T *>(smem_raw);
@@ -948,7 +983,12 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
     for (int i = 0; i < NX * NBY; ++i) acch2[i] = (acc_t){0, 0, 0, 0};
   }
   double st_s[2] = {0, 0}, st_q[2] = {0, 0};
-  double sy[NBY], qy[NBY], sw_ = 0, nz_ = 0, ng_ = 0;
+  // the Y-side sums this wave carries (DiagTab::ys, ::ws)
+  constexpr bool SUMW = YSTAT && P.ws != 0;
+  constexpr bool SUMY0 = YSTAT && P.ys[0] != 0, SUMY1 = YSTAT && NBY > 1 && P.ys[1] != 0;
+  static_assert(YSTAT == (SUMW || SUMY0 || SUMY1), "a YSTAT instantiation for a wave without Y-side sums");
+  double sy[NBY], qy[NBY], sw_ = 0;
+  int nz_ = 0, ng_ = 0;      // weights != 0 / < 0 of this item's rows: scalar counts, one update per stage
 #pragma unroll
   for (int n = 0; n < NBY; ++n) sy[n] = qy[n] = 0;
 
@@ -969,8 +1009,13 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
   }
   __syncthreads();   // B_a
   __syncthreads();   // B_-1: stage 0 is in buffer 0
+#ifdef CVM_STAMPS
+  unsigned long long t_b = 0, t_c = 0, t1, t2, t3, c_loop0, c_loop1;
+  STAMP(c_loop0);
+#endif
 
   T bf[2][NF], aw[2][NA], yf[2][NBY], wv[2];
+  T cw = (T)0;               // (SUMW) the weight of stage row lane & 15
   auto read_frags = [&](const T *buf, int ks, int slot) {
     const int r = 4 * ks + lk;
 #pragma unroll
@@ -997,14 +1042,22 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
     if (YSTAT && (!FUSEDR || ink)) {
 #pragma unroll
       for (int n = 0; n < NBY; ++n) {
-        const T yv = yf[c][n];
-        const T pv = WEIGHTED ? (T)(yv * wv[c]) : yv;
-        sy[n] += pv; qy[n] += (T)(pv * yv);
+        if (n == 0 ? SUMY0 : SUMY1) {
+          const T yv = yf[c][n];
+          const T pv = WEIGHTED ? (T)(yv * wv[c]) : yv;
+          sy[n] += pv; qy[n] += (T)(pv * yv);
+        }
       }
-      sw_ += wv[c];
-      nz_ += (wv[c] != (T)0) ? 1.0 : 0.0;
-      ng_ += (wv[c] < (T)0) ? 1.0 : 0.0;
+      if (SUMW) sw_ += wv[c];
     }
+  };
+  // (SUMW) the stage's non-zero and negative weights: rows past the end of the range read a zero weight and
+  // count as neither, an unweighted launch reads the ones line and counts rows.  Lanes 16..63 read the same
+  // sixteen words again: the low sixteen bits of the masks are the stage.
+  auto count_weights = [&]() {
+    const unsigned mz = (unsigned)__builtin_amdgcn_ballot_w64(cw != (T)0) & 0xffffu;
+    const unsigned mn = (unsigned)__builtin_amdgcn_ballot_w64(cw < (T)0) & 0xffffu;
+    nz_ += __builtin_popcount(mz); ng_ += __builtin_popcount(mn);
   };
   // MFMA i of a k-step: the G tiles in table order, then the XTY tiles
   auto mfma_i = [&](int i, int c) {
@@ -1023,6 +1076,9 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
   for (int s = sb; s < se; ++s) {
     const T *buf = smem + (s % NBUF4) * BUF_ELEMS;
     const T *nbuf = smem + ((s + 1) % NBUF4) * BUF_ELEMS;
+#ifdef CVM_STAMPS
+    STAMP(t1);
+#endif
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int c = ks & 1;
@@ -1033,6 +1089,7 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
       // and the sums of the next k-step behind the last MFMA.  NR = NF + NBY + 1 reads for NM MFMAs.
       constexpr int NR = NF + NBY + 1;
       static_assert(NR <= NM, "more fragment reads than MFMAs in a k-step");
+      static_assert(!SUMW || NR < NM, "no MFMA without an LDS read behind it for the weight count");
       const T *rb = ks < 3 ? buf : nbuf;
       const int r = 4 * (ks < 3 ? ks + 1 : 0) + lk;
 #pragma unroll
@@ -1042,11 +1099,24 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
         else if (i <= NA) bf[c ^ 1][P.rd[i - 1]] = rb[r * PITCH + 16 * P.ft[P.rd[i - 1]] + lc];
         else if (i <= NA + NBY) yf[c ^ 1][i - NA - 1] = rb[PANEL_ELEMS + r * YPITCH + 16 * (i - NA - 1) + lc];
         else if (i < NR) bf[c ^ 1][P.rd[i - 1 - NBY]] = rb[r * PITCH + 16 * P.ft[P.rd[i - 1 - NBY]] + lc];
+        else if (SUMW && i == NR && (!FUSEDR || ink)) {
+          // the weight count of THIS stage: the read behind the first free MFMA of k-step 0, the two compares
+          // two k-steps later (buffer s is not written again before B_s)
+          if (ks == 0) cw = buf[2 * PANEL_ELEMS + lc];
+          else if (ks == 2) count_weights();
+        }
         if (i == NM - 1) prepare(c ^ 1);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+#ifdef CVM_STAMPS
+    STAMP(t2);
+#endif
     __syncthreads();   // B_s
+#ifdef CVM_STAMPS
+    STAMP(t3);
+    t_b += t2 - t1; t_c += t3 - t2;
+#endif
   }
   if constexpr (TWO_LEVEL) {
     if (se < nstages) {
@@ -1063,6 +1133,9 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
 #pragma unroll
     for (int i = 0; i < NX * NBY; ++i) acch[i] = acch2[i] + acch[i];
   }
+#ifdef CVM_STAMPS
+  STAMP(c_loop1);
+#endif
 
   if constexpr (FUSEDR) {
     // ---- fused epilogue (one unit per fold): the four waves put their tiles of the upper
@@ -1092,8 +1165,8 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
         return ((v + v1) + v2) + v3;
       };
       double *tot = stl + 322;                                      // [0] sw_V, [1] nz_V
-      if (YSTAT) {
-        const double swv = comb(sw_), nzv = comb(nz_);
+      if (SUMW) {
+        const double swv = comb(sw_), nzv = (double)nz_;
         if (lane == 0) { tot[0] = swv; tot[1] = nzv; }
       }
       lds_barrier();
@@ -1134,6 +1207,8 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
       if (YSTAT) {
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
+          // Y tile n: the wave that summed it; a tile the call does not have: the wave that summed the weights
+          if (!(n < NBY ? (n == 0 ? SUMY0 : SUMY1) : SUMW)) continue;
           const int col = 16 * n + lc;
           double mu = 0.0, isd = 1.0, sd = 1.0;
           if (n < NBY) {
@@ -1149,7 +1224,7 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
           }
           if (lk == 0) { stl[256 + col] = mu; stl[288 + col] = isd; }
         }
-        if (lane == 0) {
+        if (SUMW && lane == 0) {
           stl[320] = swt_;
           if (a.out_fold && ti == 0) { double *o = a.out_fold + 4 * fo; o[0] = swt_; o[1] = nzt; o[2] = swv; o[3] = nzv; }
         }
@@ -1225,15 +1300,18 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
   if (YSTAT) {
 #pragma unroll
     for (int n = 0; n < NBY; ++n) {
+      if (!(n == 0 ? SUMY0 : SUMY1)) continue;
       const double sv = comb(sy[n]), qv = comb(qy[n]);
       if (lk == 0) { st[2 * g.Kp + 16 * n + lc] = sv; st[2 * g.Kp + g.Mp + 16 * n + lc] = qv; }
     }
-    if (NBY == 1 && lk == 0) { st[2 * g.Kp + 16 + lc] = 0.0; st[2 * g.Kp + g.Mp + 16 + lc] = 0.0; }
-    const double swv = comb(sw_), nzv = comb(nz_), ngv = comb(ng_);
-    if (lane == 0) {
-      st[2 * g.Kp + 2 * g.Mp + 0] = swv;
-      st[2 * g.Kp + 2 * g.Mp + 1] = nzv;
-      st[2 * g.Kp + 2 * g.Mp + 2] = ngv;
+    if (SUMW) {
+      if (NBY == 1 && lk == 0) { st[2 * g.Kp + 16 + lc] = 0.0; st[2 * g.Kp + g.Mp + 16 + lc] = 0.0; }
+      const double swv = comb(sw_);
+      if (lane == 0) {
+        st[2 * g.Kp + 2 * g.Mp + 0] = swv;
+        st[2 * g.Kp + 2 * g.Mp + 1] = (double)nz_;
+        st[2 * g.Kp + 2 * g.Mp + 2] = (double)ng_;
+      }
     }
   }
   if (g.M > 0) {
@@ -1253,6 +1331,19 @@ __device__ __noinline__ ROLE_ATTR void wgram4_diag_body(kargs_ptr<T> kargs, int 
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       partial_store(&tp[(16 * P.ft[P.at[P.ga[j]]] + MF<T>::drow(lane, r)) * TILE + 16 * P.ft[P.gb[j]] + lc], acc[j][r]);
+#ifdef CVM_STAMPS
+  {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned long long c_exit = __builtin_amdgcn_s_memtime();
+    if (lane == 0 && uni(slot_q) < CVM_ITEM_STAMP_STRIDE) {
+      unsigned long long *o = g_stamps5 + ((size_t)(uni(xcd_q) * CVM_ITEM_STAMP_STRIDE + uni(slot_q)) * 4 + W) * 8;
+      o[0] = c_entry; o[1] = c_loop0 - c_entry; o[2] = c_loop1 - c_loop0; o[3] = t_b; o[4] = t_c;
+      o[5] = (unsigned long long)nstages;
+      o[6] = (unsigned long long)(ti | (ti << 8)) | ((unsigned long long)blockIdx.x << 32);
+      o[7] = c_exit;
+    }
+  }
+#endif
   ROLE_EXIT();
 }
 
@@ -1269,17 +1360,22 @@ __device__ __forceinline__ void wgram4_item(const WgramArgs<T> &a, kargs_ptr<T> 
   if (FUSED && diag && do_g) {
     // diagonal tile of the fused route: the balanced waves with the fused epilogue
     const bool wide = g.M > 16;
-#define CVM_DIAGF(WV)                                                                        \
-    do {                                                                                     \
-      if (wide) wgram4_diag_body<T, WEIGHTED, GATHER, WV, 2, false, true>(kargs, xq, sq);       \
-      else wgram4_diag_body<T, WEIGHTED, GATHER, WV, 1, false, true>(kargs, xq, sq);            \
+    // (statistics formed in the launch: + the Y columns, sw, nz on the waves DiagTab names)
+    const bool ys = a.stat_flags != nullptr;
+#define CVM_DIAGF(WV)                                                                                            \
+    do {                                                                                                         \
+      if (wide) {                                                                                                \
+        if (ys) wgram4_diag_body<T, WEIGHTED, GATHER, WV, 2, diag_ystat_wave(WV, 2), true>(kargs, xq, sq);       \
+        else wgram4_diag_body<T, WEIGHTED, GATHER, WV, 2, false, true>(kargs, xq, sq);                           \
+      } else {                                                                                                   \
+        if (ys) wgram4_diag_body<T, WEIGHTED, GATHER, WV, 1, diag_ystat_wave(WV, 1), true>(kargs, xq, sq);       \
+        else wgram4_diag_body<T, WEIGHTED, GATHER, WV, 1, false, true>(kargs, xq, sq);                           \
+      }                                                                                                          \
     } while (0)
     if (wave == 0) CVM_DIAGF(0);
     else if (wave == 1) CVM_DIAGF(1);
     else if (wave == 2) CVM_DIAGF(2);
-    else if (!a.stat_flags) CVM_DIAGF(3);
-    else if (wide) wgram4_diag_body<T, WEIGHTED, GATHER, 3, 2, true, true>(kargs, xq, sq);     // (+ the Y columns, sw, nz)
-    else wgram4_diag_body<T, WEIGHTED, GATHER, 3, 1, true, true>(kargs, xq, sq);
+    else CVM_DIAGF(3);
 #undef CVM_DIAGF
     return;
   }
@@ -1292,17 +1388,20 @@ __device__ __forceinline__ void wgram4_item(const WgramArgs<T> &a, kargs_ptr<T> 
   if (diag && do_g) {
     // diagonal tile, first Y chunk: the four balanced waves (see wgram4_diag_body)
     const bool wide = g.M > 16, ys = (ti == 0);
-#define CVM_DIAG(WV)                                                                         \
-    do {                                                                                     \
-      if (wide) wgram4_diag_body<T, WEIGHTED, GATHER, WV, 2, false>(kargs, xq, sq);             \
-      else wgram4_diag_body<T, WEIGHTED, GATHER, WV, 1, false>(kargs, xq, sq);                  \
+#define CVM_DIAG(WV)                                                                                             \
+    do {                                                                                                         \
+      if (wide) {                                                                                                \
+        if (ys) wgram4_diag_body<T, WEIGHTED, GATHER, WV, 2, diag_ystat_wave(WV, 2)>(kargs, xq, sq);             \
+        else wgram4_diag_body<T, WEIGHTED, GATHER, WV, 2, false>(kargs, xq, sq);                                 \
+      } else {                                                                                                   \
+        if (ys) wgram4_diag_body<T, WEIGHTED, GATHER, WV, 1, diag_ystat_wave(WV, 1)>(kargs, xq, sq);             \
+        else wgram4_diag_body<T, WEIGHTED, GATHER, WV, 1, false>(kargs, xq, sq);                                 \
+      }                                                                                                          \
     } while (0)
     if (wave == 0) CVM_DIAG(0);
     else if (wave == 1) CVM_DIAG(1);
     else if (wave == 2) CVM_DIAG(2);
-    else if (!ys) CVM_DIAG(3);
-    else if (wide) wgram4_diag_body<T, WEIGHTED, GATHER, 3, 2, true>(kargs, xq, sq);
-    else wgram4_diag_body<T, WEIGHTED, GATHER, 3, 1, true>(kargs, xq, sq);
+    else CVM_DIAG(3);
 #undef CVM_DIAG
     return;
   }

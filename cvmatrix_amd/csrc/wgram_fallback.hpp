@@ -33,6 +33,11 @@ __device__ unsigned long long g_stamps[1024 * 8 * 4];
 __device__ unsigned long long g_stamps2[1024 * 8 * 4];
 __device__ unsigned long long g_stamps4[1024 * 8];   // fused off-diagonal epilogue, wave 0: 8 time points
 __device__ unsigned long long g_stamps3[1024 * 8 * 2];   // per compute wave: prologue, epilogue cycles   // per wave: shader cycles, 100 MHz ticks, start tick
+// per (work item = xcd * CVM_ITEM_STAMP_STRIDE + list position, compute wave) of wgram4_kernel: entry (s_memtime), cycles
+// entry -> stage 0 ready, loop cycles, of those computing / waiting at the stage barriers, stages,
+// ti | tj << 8 | yc << 16 | workgroup << 32, exit (s_memtime).  tools/item_stamps.py reads it.
+constexpr int CVM_ITEM_STAMP_STRIDE = 128, CVM_ITEM_STAMPS = 8 * CVM_ITEM_STAMP_STRIDE;
+__device__ unsigned long long g_stamps5[CVM_ITEM_STAMPS * 4 * 8];
 #define STAMP(v) do { __builtin_amdgcn_sched_barrier(0); v = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); } while (0)
 #endif
 
