@@ -14,6 +14,13 @@
 // other's slices: the spin limit then reports status 1 instead of hanging; run one at a time.)
 // With S == 1 (many folds) the barrier is a __syncthreads().  All arithmetic in float64; fixed
 // summation orders, no float atomics: results do not depend on scheduling.
+//
+// Non-finite input.  A fold with a NaN or an infinity anywhere in its XTX or XTY is handed back as NaN
+// throughout (every component of B, W, P, Q, R) with n_fit -1, never as finite numbers: the stopping
+// rule below would otherwise read a NaN norm as "nothing left to extract" and leave zeros.  The fold is
+// recognised by numbers every slice of it holds identically anyway -- the trace of XTY^T XTY, |w|^2,
+// t^T t -- so the slices leave the component loop together; no barrier, exchange slot or pass over
+// data is added.  (An overflow inside a fold of finite numbers ends the same way.)
 #pragma once
 
 constexpr int PLS_THREADS = 512;
@@ -108,6 +115,35 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
 #pragma unroll
   for (int w = 0; w < PLS_NW; ++w) t += red[w];
   return t;
+}
+
+// neither NaN nor an infinity
+__device__ __forceinline__ bool pls_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
+
+// What a fold with non-finite input gets (see the head of this file): NaN over all A components of the
+// outputs this slice owns -- rows [k0, k0 + n) of B, W, P, R; Q and n_fit by slice 0.  Called by all
+// threads of the workgroup once the component loop is left; the components written before wait behind
+// the barrier so that the NaN is what stays.
+template <typename T>
+__device__ __forceinline__ void pls_poison_fold(void *B, void *W, void *P, void *Q, void *R, int *n_fit, int f, int s,
+                                                int K, int M, int A, int k0, int n, int tid) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const T nan = (T)__builtin_nan("");
+  for (int c = 0; c < A; ++c) {
+    T *Bout = (T *)B + (((size_t)f * A + c) * K + k0) * M;
+    for (int e = tid; e < n * M; e += PLS_THREADS) Bout[e] = nan;
+  }
+  for (int e = tid; e < n * A; e += PLS_THREADS) {
+    const size_t o = ((size_t)f * K + k0) * A + e;            // rows k0 ... of [K][A]: contiguous
+    if (W) ((T *)W)[o] = nan;
+    if (R) ((T *)R)[o] = nan;
+    if (P) ((T *)P)[o] = nan;
+  }
+  if (s == 0) {
+    if (Q) for (int e = tid; e < M * A; e += PLS_THREADS) ((T *)Q)[(size_t)f * M * A + e] = nan;
+    if (tid == 0) n_fit[f] = -1;
+  }
 }
 
 // Numbers traded between the slices of a fold.  SLICED: device-coherent accesses (sc1: they go
@@ -434,14 +470,15 @@ __device__ __forceinline__ double *pls_eig_lds(const double *S0, double tr, int 
 #else
 #define PLS_QSTAMP(i)
 #endif
-__device__ __forceinline__ void pls_dominant_q(const double *S0, double *Ba, double *Bb, double *trp, double *qv,
+// Returns false (q = 0) when the trace is not finite: the fold holds a NaN or an infinity.
+__device__ __forceinline__ bool pls_dominant_q(const double *S0, double *Ba, double *Bb, double *trp, double *qv,
                                                int M, int tid, unsigned long long *stamp_p = nullptr) {
   const int lane = tid & 63, wave = tid >> 6;
   const double tr = wave_sum(lane < M ? S0[(size_t)lane * M + lane] : 0.0);
-  if (!(tr > 0.0)) {
+  if (!(tr > 0.0) || !pls_finite(tr)) {
     if (tid < M) qv[tid] = 0.0;
     __syncthreads();
-    return;
+    return pls_finite(tr);
   }
   double *fin = Ba;                                            // the (nearly) rank-one power of S
   if (M <= 32) {
@@ -475,10 +512,12 @@ __device__ __forceinline__ void pls_dominant_q(const double *S0, double *Ba, dou
     if (tid < M) qv[tid] = nn > 0.0 ? v / nn : 0.0;
     __syncthreads();
   }
+  return true;
 }
 
 // dst[p] = sum over the S slices of x[t * len + p], p in [0, len): a thread per element, the
-// loads of 16 slices in flight at a time, summed in slice order
+// loads of 16 slices in flight at a time and summed as a tree, the sixteens in slice order (one chain
+// over S = 115 slices put |w| 7 u away from 1: the norm is the sum of the slices' parts)
 template <bool SLICED>
 __device__ __forceinline__ void xreduce(const double *x, int len, int S, double *dst, int tid) {
   if constexpr (!SLICED) {
@@ -491,7 +530,10 @@ __device__ __forceinline__ void xreduce(const double *x, int len, int S, double 
 #pragma unroll
         for (int u = 0; u < 16; ++u) v[u] = (t0 + u < S) ? xget<true>(&x[(size_t)(t0 + u) * len + p]) : 0.0;
 #pragma unroll
-        for (int u = 0; u < 16; ++u) acc += v[u];
+        for (int h = 8; h >= 1; h >>= 1)
+#pragma unroll
+          for (int u = 0; u < h; ++u) v[u] += v[u + h];
+        acc += v[0];
       }
       dst[p] = acc;
     }
@@ -565,6 +607,7 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_kernel(const PlsArgs a) {
   PLS_STAMP(0);
 
   int fit = 0;
+  bool bad = false;                                            // non-finite input (the same in every slice of the fold)
   for (int c = 0; c < A; ++c) {
     if (M > 1) {
       // ---- 1: partial XTY^T XTY of the slice's rows ----------------------------------------
@@ -582,10 +625,11 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_kernel(const PlsArgs a) {
       __syncthreads();
 #ifdef CVM_STAMPS
       if (blockIdx.x == 0 && tid == 0) g_pls_stamps[14] += __builtin_readcyclecounter() - stamp_;
-      pls_dominant_q(S0, Ba, Bb, ms, qv, M, tid, &stamp_);
+      bad = !pls_dominant_q(S0, Ba, Bb, ms, qv, M, tid, &stamp_);
 #else
-      pls_dominant_q(S0, Ba, Bb, ms, qv, M, tid);
+      bad = !pls_dominant_q(S0, Ba, Bb, ms, qv, M, tid);
 #endif
+      if (bad) break;                                          // (uniform: every slice summed the same S0)
     }
     PLS_STAMP(3);
     // ---- 2b: w of the slice (not normalised yet), its partial norm and partial P^T w -------
@@ -631,6 +675,7 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_kernel(const PlsArgs a) {
     xreduce<SLICED>(x_2, 1 + c, S, cx, tid);
     __syncthreads();
     const double nrm = sqrt(cx[0]);
+    if (!pls_finite(nrm)) { bad = true; break; }               // (uniform, like the stop below)
     if (!(nrm > a.eps)) break;                                 // nothing left to extract (uniform)
     for (int j = tid; j < c; j += PLS_THREADS) cj[j] = cj[j] / nrm;
     __syncthreads();
@@ -703,6 +748,7 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_kernel(const PlsArgs a) {
     xreduce<SLICED>(x_4, 1 + M, S, qx, tid);
     __syncthreads();
     const double tTt = qx[0];
+    if (!pls_finite(tTt)) { bad = true; break; }               // (uniform: behind the last barrier of the component)
     const double qmine = tid < M ? qv[tid] / tTt : 0.0;
     if (tid < M) {
       qv[tid] = qmine;
@@ -738,6 +784,10 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_kernel(const PlsArgs a) {
     __syncthreads();
     PLS_STAMP(11);
     fit = c + 1;
+  }
+  if (bad) {
+    pls_poison_fold<T>(a.B, a.W, a.P, a.Q, a.R, a.n_fit, f, s, K, M, A, k0, n, tid);
+    return;
   }
   // components that could not be extracted stay zero
   for (int c = fit; c < A; ++c) {
@@ -822,6 +872,7 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_rep_kernel(const PlsArgs a) {
   __syncthreads();
 
   int fit = 0;
+  bool bad = false;                                            // non-finite input (every slice computes the same numbers)
   for (int c = 0; c < A; ++c) {
     if (M > 1) {
       // ---- XTY^T XTY over all rows, its dominant eigenvector q (as in pls_kernel, nothing traded)
@@ -830,7 +881,8 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_rep_kernel(const PlsArgs a) {
       else if (M <= 48) pls_gram_phase_tri<3, false>(Yl, yst, K, M, ms, S0, tid);
       else pls_gram_phase_tri<4, false>(Yl, yst, K, M, ms, S0, tid);
       __syncthreads();
-      pls_dominant_q(S0, Ba, Bb, ms, qv, M, tid);
+      bad = !pls_dominant_q(S0, Ba, Bb, ms, qv, M, tid);
+      if (bad) break;
     }
     // ---- w (all rows), its norm, P^T w ---------------------------------------------------------
     double nrm2 = 0.0;
@@ -846,6 +898,7 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_rep_kernel(const PlsArgs a) {
     }
     nrm2 = block_sum(nrm2, red);                               // (ends behind a barrier: wl is visible)
     const double nrm = sqrt(nrm2);
+    if (!pls_finite(nrm)) { bad = true; break; }
     if (!(nrm > a.eps)) break;                                 // every slice sees the same number
     for (int j0 = wave * 4; j0 < c; j0 += 4 * PLS_NW) {
       double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -921,6 +974,7 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_rep_kernel(const PlsArgs a) {
     double tt = 0.0;
     for (int k = tid; k < K; k += PLS_THREADS) tt += rl[k] * ul[k];
     tt = block_sum(tt, red);
+    if (!pls_finite(tt)) { bad = true; break; }                // (behind the component's barrier: no slice waits any more)
     for (int j = wave; j < M; j += PLS_NW) {
       double acc = 0.0;
       for (int k = lane; k < K; k += 64) acc += Yl[(size_t)k * yst + j] * rl[k];
@@ -951,6 +1005,10 @@ __global__ __launch_bounds__(PLS_THREADS) void pls_rep_kernel(const PlsArgs a) {
     }
     __syncthreads();
     fit = c + 1;
+  }
+  if (bad) {
+    pls_poison_fold<T>(a.B, a.W, a.P, a.Q, a.R, a.n_fit, f, s, K, M, A, k0, n, tid);
+    return;
   }
   for (int c = fit; c < A; ++c) {
     T *Bout = (T *)a.B + (((size_t)f * A + c) * K + k0) * M;

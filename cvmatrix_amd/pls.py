@@ -22,7 +22,9 @@ MAX_COMPONENTS = 512
 class PLSFit(NamedTuple):
     """``B`` (F,A,K,M): ``B[f, a]`` = regression coefficients with ``a + 1`` components;
     ``W, P, R`` (F,K,A) and ``Q`` (F,M,A) when requested, else None; ``n_fit`` (F,) int32:
-    components extracted per fold (less than A only when XTY deflated to zero)."""
+    components extracted per fold (less than A only when XTY deflated to zero: the components
+    beyond are exactly zero).  A fold whose XTX or XTY holds a NaN or an infinity has ``n_fit`` -1
+    and NaN in every component of ``B, W, P, Q, R``."""
     B: torch.Tensor
     W: Optional[torch.Tensor]
     P: Optional[torch.Tensor]
@@ -54,7 +56,13 @@ def pls_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, A: int, *, return_fact
     barrier times out and the library recomputes every fold with one workgroup per fold in the same call;
     only where a fold does not fit one workgroup's LDS are the outputs overwritten with NaN (``n_fit`` -1) --
     ``check=True`` synchronises once to turn that case into an exception.  Nothing half-written is ever
-    returned."""
+    returned.
+
+    Non-finite input: a fold with a NaN or an infinity anywhere in its ``XTX`` or ``XTY`` (what the fold stage
+    hands over for a fold it could not compute) comes back as NaN in every component of ``B, W, P, Q, R`` with
+    ``n_fit`` -1 -- never as zeros or other finite numbers, so ``pls_validation_sse`` and ``cv_rmse`` turn it
+    into NaN errors, not into the finite error of predicting the training mean.  The status stays 0 (no
+    exception) and every other fold has the bits it has when that fold is clean."""
     if not (isinstance(XTX, torch.Tensor) and XTX.is_cuda and isinstance(XTY, torch.Tensor) and XTY.is_cuda):
         raise TypeError("pls_fit_batched takes device tensors (the batched training matrices).")
     if XTX.dim() == 2:

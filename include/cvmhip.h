@@ -237,7 +237,13 @@ int cvm_partition_periodic(const int64_t *labels, int64_t N, int64_t n_labels, c
  *                            valid); 1 only where a fold does not fit one workgroup's LDS -- the outputs are
  *                            then NaN and n_fit -1, never half-written
  * Component signs are those of the dominant eigenvector found by repeated squaring of XTY^T XTY;
- * B does not depend on them.  Arithmetic in float64 for both dtypes. */
+ * B does not depend on them.  Arithmetic in float64 for both dtypes.
+ * Non-finite input: a fold with a NaN or an infinity anywhere in its XTX or XTY has B, W, P, Q, R all NaN
+ * for every component and n_fit -1 (never zeros or other finite numbers: a fold that cvm_fold_update
+ * handed over as NaN stays NaN through cvm_pls_validation_sse); status stays 0 and every other fold has
+ * the bits it has when that fold is clean.  A fold of finite numbers whose arithmetic overflows ends the
+ * same way.  A fold's bits depend on its own matrices and on the plan (cvm_pls_plan), not on its place
+ * in the batch or on what the workspace held. */
 size_t cvm_pls_workspace_bytes(int64_t n_folds, int K, int M, int A, int dtype);
 int cvm_pls_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
                 void *B, void *W, void *P, void *Q, void *R, int32_t *n_fit, int32_t *status,

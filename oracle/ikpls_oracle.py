@@ -37,12 +37,84 @@ from __future__ import annotations
 import numpy as np
 
 
-def ikpls_fit(XTX: np.ndarray, XTY: np.ndarray, A: int):
+def dominant_q_squaring(S: np.ndarray) -> np.ndarray:
+    """The dominant eigenvector of the symmetric positive semi-definite ``S`` the way the device
+    kernel says it finds it (``pls_dominant_q``, cvmatrix_amd/csrc/pls.hpp), restated in float64 NumPy:
+    ``m = S / trace``; ``m <- m^2 / sum(m^2)`` (``sum(m^2)`` of the symmetric trace-1 input is
+    ``sum lambda^2``) until ``1 - sum(m^2) < 1e-13`` or 64 squarings; the column of the largest diagonal
+    entry, the lowest index among equals; two power steps with ``S`` itself, each normalised.  A trace
+    that is not positive gives the zero vector.  It is a statement of the method, not of the kernel's
+    summation orders: its Rayleigh quotient is the yardstick for the kernel's, its bits are not."""
+    S = np.asarray(S, dtype=np.float64)
+    M = S.shape[0]
+    tr = float(np.trace(S))
+    if not tr > 0.0:
+        return np.zeros(M)
+    m = S / tr
+    for _ in range(64):
+        t2 = float(np.sum(m * m))
+        m = (m @ m) / t2
+        if 1.0 - t2 < 1e-13:
+            break
+    q = m[:, int(np.argmax(np.maximum(np.diag(m), 0.0)))].copy()       # argmax: the first among equals
+    for _ in range(2):
+        v = S @ q
+        nn = float(np.sqrt(v @ v))
+        q = v / nn if nn > 0.0 else np.zeros(M)
+    return q
+
+
+def ikpls_follow(XTX: np.ndarray, XTY: np.ndarray, W: np.ndarray, dtype=np.longdouble):
+    """The published algorithm with the weight vector of component ``a`` GIVEN (``W[:, a]``, taken as it
+    is: neither recomputed nor normalised) and everything else computed in ``dtype``: given the same
+    weights, r, u = XTX r, tTt, p, q, the deflation and B are determined, so a fit can be compared
+    with a reference that does not have to find an eigenvector.  Plain loops and ``@``.
+
+    Returns ``(B, P, Q, R, tTt, Ys)``: ``B`` (A,K,M); ``P, R`` (K,A); ``Q`` (M,A); ``tTt`` (A,);
+    ``Ys`` (A,K,M), the deflated XTY BEFORE each component.  With ``dtype=np.float64`` the operations
+    and their order are those of ``ikpls_fit`` (the same bits from the same weights)."""
+    dt = np.dtype(dtype)
+    if dt == np.longdouble:
+        assert np.finfo(np.longdouble).eps < 2e-19, "np.longdouble is not the x86 80-bit format here"
+    XTX = np.asarray(XTX).astype(dt)
+    Y = np.array(XTY, dtype=dt, copy=True)
+    if Y.ndim == 1:
+        Y = Y.reshape(-1, 1)
+    W = np.asarray(W).astype(dt)
+    K, M = Y.shape
+    A = W.shape[1]
+    B = np.zeros((A, K, M), dt)
+    P = np.zeros((K, A), dt)
+    Q = np.zeros((M, A), dt)
+    R = np.zeros((K, A), dt)
+    tTt = np.zeros(A, dt)
+    Ys = np.zeros((A, K, M), dt)
+    for a in range(A):
+        Ys[a] = Y
+        w = W[:, a]
+        r = w.copy()
+        if a:
+            r -= R[:, :a] @ (P[:, :a].T @ w)
+        u = XTX @ r
+        t = r @ u
+        p = u / t
+        q = (Y.T @ r) / t
+        Y -= np.outer(p, q) * t
+        P[:, a], Q[:, a], R[:, a], tTt[a] = p, q, r, t
+        B[a] = (B[a - 1] if a else 0) + np.outer(r, q)
+    return B, P, Q, R, tTt, Ys
+
+
+def ikpls_fit(XTX: np.ndarray, XTY: np.ndarray, A: int, eig: str = "eigh"):
     """Returns ``(B, W, P, Q, R, n_fit)`` with ``B`` (A,K,M); ``W, P, R`` (K,A); ``Q`` (M,A).
 
     ``B[a]`` are the regression coefficients of the model with ``a + 1`` components, for
-    centred/scaled predictors and responses exactly as ``XTX``/``XTY`` were.
+    centred/scaled predictors and responses exactly as ``XTX``/``XTY`` were.  ``eig``: where the
+    eigenvector of XTY^T XTY comes from for M > 1 -- "eigh" (LAPACK) or "squaring"
+    (``dominant_q_squaring``, the device kernel's method).
     """
+    if eig not in ("eigh", "squaring"):
+        raise ValueError("eig must be 'eigh' or 'squaring'")
     XTX = np.asarray(XTX)
     dtype = XTX.dtype
     XTY = np.array(XTY, dtype=dtype, copy=True)
@@ -61,8 +133,11 @@ def ikpls_fit(XTX: np.ndarray, XTY: np.ndarray, A: int):
             w = XTY[:, 0].copy()
         else:
             S = XTY.T @ XTY
-            _, vecs = np.linalg.eigh(S)
-            w = XTY @ vecs[:, -1]
+            if eig == "squaring":
+                w = XTY @ dominant_q_squaring(S)
+            else:
+                _, vecs = np.linalg.eigh(S)
+                w = XTY @ vecs[:, -1]
         nrm = np.sqrt(w @ w)
         if not nrm > eps:
             break
