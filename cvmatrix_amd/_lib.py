@@ -31,6 +31,7 @@ EXPORTS = (
     "cvm_pls_workspace_bytes", "cvm_pls_fit", "cvm_pls_plan",
     "cvm_pls_sse_workspace_bytes", "cvm_pls_validation_sse",
     "cvm_ridge_workspace_bytes", "cvm_ridge_fit",
+    "cvm_pcr_workspace_bytes", "cvm_pcr_fit",
 )
 
 _lib = None
@@ -121,6 +122,10 @@ def load():
     lib.cvm_ridge_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
     lib.cvm_ridge_fit.restype = C.c_int
     lib.cvm_ridge_fit.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, sz, vp]
+    lib.cvm_pcr_workspace_bytes.restype = sz
+    lib.cvm_pcr_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.cvm_pcr_fit.restype = C.c_int
+    lib.cvm_pcr_fit.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, dbl, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.cvm_timing_enable.restype = C.c_int
     lib.cvm_timing_enable.argtypes = [C.c_int]
     lib.cvm_timing_read.restype = C.c_int

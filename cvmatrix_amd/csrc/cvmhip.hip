@@ -45,6 +45,7 @@ namespace {
 #include "partition.hpp"
 #include "pls.hpp"
 #include "ridge.hpp"
+#include "pcr.hpp"
 
 }  // namespace
 
@@ -359,6 +360,30 @@ int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int 
   if (dtype == CVM_F32)
     return ridge_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_ridge_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A) {
+  if (n_folds < 0 || K <= 0 || K > PCR_MAXK || M < 0 || M > PCR_MAXM || A <= 0 || A > K) return 0;
+  return pcr_workspace_bytes(n_folds, K, M);
+}
+
+int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype, double rank_tol,
+                void *B, double *eigenvalues, void *V, int32_t *n_fit, int32_t *sweeps, void *ws, size_t ws_bytes,
+                void *stream) {
+  if (!XTX || !eigenvalues || !n_fit || !sweeps || !ws) return fail(CVM_EINVAL, "cvm_pcr_fit: null pointer%s");
+  if (n_folds < 0 || K <= 0 || K > PCR_MAXK || M < 0 || M > PCR_MAXM || A <= 0 || A > K)
+    return fail(CVM_EINVAL, "cvm_pcr_fit: bad shape (1 <= K <= 512, 1 <= A <= K, 0 <= M <= 64)%s");
+  if (M > 0 ? (!XTY || !B) : (XTY || B))
+    return fail(CVM_EINVAL, "cvm_pcr_fit: XTY and B go with M > 0, neither with M == 0 (PCA only)%s");
+  if (!(rank_tol < 1.0)) return fail(CVM_EINVAL, "cvm_pcr_fit: rank_tol must be below 1 (<= 0: the default)%s");
+  if (rank_tol <= 0.0) rank_tol = 32.0 * K * 0x1p-52;
+  if (dtype == CVM_F64)
+    return pcr_fit_impl<double>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
+                                (hipStream_t)stream);
+  if (dtype == CVM_F32)
+    return pcr_fit_impl<float>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
+                               (hipStream_t)stream);
+  return fail(CVM_EINVAL, "cvm_pcr_fit: dtype must be CVM_F32 or CVM_F64%s");
 }
 
 int cvm_pls_plan(int64_t n_folds, int K, int M, int A, int dtype, int64_t *info) {

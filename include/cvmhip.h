@@ -286,6 +286,42 @@ int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const in
 size_t cvm_ridge_workspace_bytes(int64_t n_folds, int K, int M, int L);
 int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
                   int dtype, void *B, int32_t *info, void *ws, size_t ws_bytes, void *stream);
+/* PCA and principal component regression for every fold (the two consumers of the training matrices that
+ * the reference's CVMatrix docstring names next to PLS and OLS): the A leading eigenpairs of XTX[f],
+ *   XTX[f] v_j = lambda_j v_j,  lambda_0 >= lambda_1 >= ...,
+ * and the regression coefficients on the first a+1 components
+ *   B[f][a] = sum over j <= a of v_j (v_j^T XTY[f]) / lambda_j
+ * by a cyclic two-sided Jacobi iteration in a fixed round-robin order, one workgroup per fold.
+ *   XTX [n_folds][K][K], XTY [n_folds][K][M]   the out_XTX / out_XTY of cvm_fold_update (not modified;
+ *                        XTX is taken as symmetric), 1 <= K <= 512, 1 <= A <= K, 0 <= M <= 64;
+ *                        M == 0 with XTY == NULL and B == NULL: PCA only
+ *   rank_tol     components with lambda_j <= rank_tol * lambda_0 do not exist; <= 0: the default
+ *                32 K 2^-52 (the backward error of the method, below which an eigenvalue cannot be told
+ *                from zero); NaN or >= 1: CVM_EINVAL
+ *   B    [n_folds][A][K][M] in `dtype`: the layout cvm_pls_validation_sse scores.  Summed in the order
+ *        j = 0, 1, ...; for a >= n_fit[f], B[f][a] has the bits of B[f][n_fit[f] - 1] (all zeros if
+ *        n_fit[f] == 0): the model with more components than exist is the model with all that exist
+ *   eigenvalues  float64 [n_folds][A] for both dtypes, as computed (may be tiny or slightly negative)
+ *   V    [n_folds][K][A] in `dtype` (may be NULL): the components; in each the entry of largest magnitude
+ *        is positive (the lowest index among equals); components a >= n_fit[f] are exactly zero
+ *   n_fit  int32[n_folds]: min(A, number of lambda_j > rank_tol * lambda_0)
+ *   sweeps int32[n_folds]: Jacobi sweeps run (the last one made no rotation), 1 .. 60
+ *   ws   cvm_pcr_workspace_bytes(n_folds, K, M, A) for min(n_folds, 512) folds in flight (host arithmetic,
+ *        no device query): slots of 2 K ld float64, ld = max(K, M) rounded up to 4, each 256-byte aligned;
+ *        any smaller workspace that holds one slot runs fewer folds at a time with the same results to
+ *        the bit.  Less than one slot: CVM_EWORKSPACE.  Bad pointers, shapes, rank_tol or dtype:
+ *        CVM_EINVAL (cvm_pcr_workspace_bytes: 0).  n_folds == 0: nothing is launched.
+ * Non-finite input: a fold with a NaN or an infinity anywhere in its XTX or XTY (or whose Frobenius norm
+ * overflows) has B, V and eigenvalues all NaN, n_fit -1 and sweeps 0, as cvm_pls_fit has it: a fold that
+ * cvm_fold_update handed over as NaN stays NaN through cvm_pls_validation_sse.  A fold that has not
+ * converged after 60 sweeps: the same outputs with sweeps -1.  Every other fold is unaffected.
+ * Arithmetic in float64 for both dtypes (float32 inputs widened on load, outputs rounded once on store),
+ * no float atomics, every sum in a fixed order; a fold's bits depend on its own matrices alone, not on its
+ * place in the batch, the batch size, the workspace size or what the workspace held. */
+size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A);
+int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
+                double rank_tol, void *B, double *eigenvalues, void *V, int32_t *n_fit, int32_t *sweeps,
+                void *ws, size_t ws_bytes, void *stream);
 /* info[0]=row slices per fold, [1]=rows per slice, [2]=folds per launch, [3]=1 if the slice of XTX
  * stays in LDS, 0 if it is streamed, 2: few folds -- the kernel that keeps the small state of a fold
  * (deflated XTY, P, R) whole in every slice and passes ONE per-fold barrier per component, XTX
