@@ -46,6 +46,7 @@ namespace {
 #include "pls.hpp"
 #include "ridge.hpp"
 #include "pcr.hpp"
+#include "predict.hpp"
 
 }  // namespace
 
@@ -384,6 +385,46 @@ int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
     return pcr_fit_impl<float>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
                                (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_pcr_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+// shapes of cvm_cv_predict / cvm_cv_predict_plan: an error message, or nullptr
+static const char *predict_bad_shape(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int K, int M, int A, int dtype) {
+  if (n_folds < 0 || max_fold_rows < 0 || K <= 0 || A <= 0 || ldX < K) return "cvm_cv_predict: bad shape%s";
+  if (M <= 0 || M > PLS_MAXM) return "cvm_cv_predict: 1 <= M <= 64 responses%s";
+  if (A > PLS_MAXA) return "cvm_cv_predict: at most 512 models per fold%s";
+  if (dtype != CVM_F64 && dtype != CVM_F32) return "cvm_cv_predict: dtype must be CVM_F32 or CVM_F64%s";
+  // (folds x groups x chunks is counted in 64 bits: 2^40 folds of 2^40 rows are refused here, not wrapped)
+  if (n_folds > ((int64_t)1 << 40) || max_fold_rows > ((int64_t)1 << 40) ||
+      (n_folds > 0 && (max_fold_rows / SSE_ROWS + 1) > (((int64_t)1 << 52) / n_folds)))
+    return "cvm_cv_predict: more than 2^61 workgroups%s";
+  return nullptr;
+}
+
+int cvm_cv_predict(const void *X, int64_t ldX, const int64_t *idx, const int64_t *offsets, int64_t n_folds,
+                   int64_t max_fold_rows, int K, int M, int A, int dtype, const void *muX, const void *sdX,
+                   const void *muY, const void *sdY, const void *B, void *out, int by_row, void *stream) {
+  // (everything below is decided before the device is touched)
+  if (!X || !offsets || !B || !out) return fail(CVM_EINVAL, "cvm_cv_predict: null pointer%s");
+  if (by_row != 0 && by_row != 1) return fail(CVM_EINVAL, "cvm_cv_predict: by_row must be 0 or 1%s");
+  if (const char *bad = predict_bad_shape(n_folds, max_fold_rows, ldX, K, M, A, dtype)) return fail(CVM_EINVAL, bad);
+  if (dtype == CVM_F64)
+    return predict_impl<double>(X, ldX, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, out, by_row,
+                                (hipStream_t)stream);
+  return predict_impl<float>(X, ldX, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, out, by_row,
+                             (hipStream_t)stream);
+}
+
+int cvm_cv_predict_plan(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int K, int M, int A, int dtype, int aligned,
+                        int64_t *info) {
+  if (!info) return fail(CVM_EINVAL, "cvm_cv_predict_plan: null pointer%s");
+  if (const char *bad = predict_bad_shape(n_folds, max_fold_rows, ldX, K, M, A, dtype)) return fail(CVM_EINVAL, bad);
+  const int esize = dtype == CVM_F64 ? 8 : 4;
+  const void *where = aligned ? nullptr : reinterpret_cast<const void *>(8);      // (stands for every address)
+  const PredictPlan p = predict_plan(n_folds, max_fold_rows, K, M, A, esize, predict_vec(16 / esize, where, ldX, K, M, where, where, where));
+  info[0] = p.nt; info[1] = p.groups; info[2] = p.chunks; info[3] = p.total; info[4] = p.launches;
+  info[5] = p.total < PREDICT_MAX_WGS ? p.total : PREDICT_MAX_WGS;
+  info[6] = (int64_t)p.lds; info[7] = p.st_in_lds; info[8] = p.vec;
+  return CVM_OK;
 }
 
 int cvm_pls_plan(int64_t n_folds, int K, int M, int A, int dtype, int64_t *info) {

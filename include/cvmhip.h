@@ -322,6 +322,44 @@ size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A);
 int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
                 double rank_tol, void *B, double *eigenvalues, void *V, int32_t *n_fit, int32_t *sweeps,
                 void *ws, size_t ws_bytes, void *stream);
+/* Out-of-fold predictions of every fold's linear models, and predictions for new rows -- what the scorer
+ * above forms and reduces to one number, stored whole (scikit-learn's cross_val_predict; no counterpart in
+ * the reference, whose consumers predict fold by fold on the host): for fold f, row i of the fold, model a
+ * and response m
+ *   out[r][a][m] = ((x_i - muX[f]) / sdX[f]) . B[f][a][:, m] * sdY[f][m] + muY[f][m]
+ *   X    rows of K elements with a row pitch of ldX >= K elements (a padded model: its pitch)
+ *   idx, offsets  device arrays as in cvm_pls_validation_sse; idx == NULL: the fold's rows are the rows
+ *        offsets[f] .. offsets[f+1]-1 of X themselves (new data: one fold, offsets {0, n})
+ *   max_fold_rows  the longest fold, from the host (the device offsets are not read back)
+ *   muX, sdX [n_folds][K], muY, sdY [n_folds][M] in `dtype`; each may be NULL: 0 for a mean, 1 for a
+ *        standard deviation
+ *   B    [n_folds][A][K][M] in `dtype`, 1 <= A <= 512, 1 <= M <= 64, K >= 1
+ *   out  [rows][A][M] in `dtype`, contiguous: the A M predictions of a row lie together.  by_row == 0: r is
+ *        the position in idx (offsets[f] + i); by_row == 1: r is the row number (the idx value) -- the caller
+ *        guarantees that no row occurs twice, and rows in no fold are not written
+ * No workspace, no atomics, any number of folds of any length (cvm_cv_predict_plan: how a call is cut into
+ * launches).  n_folds == 0: nothing is launched.  Bad pointers, shapes,
+ * by_row or dtype: CVM_EINVAL, decided before the device is touched.
+ * MFMA in `dtype`, the standardisation and the scale-and-shift in float64, one rounding to `dtype` at the
+ * store.  The sum over k runs in ONE order (stages of 16, steps of 4) on every route, and the reciprocal of
+ * sdX is formed by one formula: the bits of one prediction depend on its row of X, its fold's statistics and
+ * its column B[f][a][:, m] alone -- not on the fold's other rows, the row's place in the fold, the other
+ * folds, A, the other columns of B, ldX, by_row, the alignment of the arrays or the stream.  A NaN stays
+ * where it belongs: in the rows of X that hold it, in the folds whose B or statistics hold it. */
+int cvm_cv_predict(const void *X, int64_t ldX, const int64_t *idx, const int64_t *offsets, int64_t n_folds,
+                   int64_t max_fold_rows, int K, int M, int A, int dtype,
+                   const void *muX, const void *sdX, const void *muY, const void *sdY,
+                   const void *B, void *out, int by_row, void *stream);
+/* How cvm_cv_predict cuts a call into launches -- host arithmetic, no device: info[0] = column tiles of 16 per
+ * wave (a workgroup owns 64 rows x 64 info[0] columns), [1] = column groups, [2] = row chunks of 64 in the longest
+ * fold, [3] = workgroups in all = n_folds x [1] x [2], [4] = launches, [5] = workgroups of the largest launch,
+ * [6] = LDS bytes per workgroup, [7] = 1 if the fold's statistics are kept in LDS, [8] = 1 if rows and coefficients
+ * are read in 16-byte pieces.  `aligned`: X, B, muX and sdX are 16-byte aligned.  The HIP runtime refuses a launch
+ * of 2^32 threads or more in x, so a launch has at most 2^24 - 1 workgroups of 256 threads; the flat list of
+ * workgroups is cut wherever that falls, inside a fold too: neither the number of folds nor the length of a fold is
+ * limited by it (beyond 2^40 each, and 2^61 workgroups in all: CVM_EINVAL). */
+int cvm_cv_predict_plan(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int K, int M, int A, int dtype,
+                        int aligned, int64_t *info);
 /* info[0]=row slices per fold, [1]=rows per slice, [2]=folds per launch, [3]=1 if the slice of XTX
  * stays in LDS, 0 if it is streamed, 2: few folds -- the kernel that keeps the small state of a fold
  * (deflated XTY, P, R) whole in every slice and passes ONE per-fold barrier per component, XTX
