@@ -46,6 +46,8 @@ namespace {
 #include "pls.hpp"
 #include "ridge.hpp"
 #include "pcr.hpp"
+#include "tile_product.hpp"
+#include "validation_sse.hpp"
 #include "predict.hpp"
 
 }  // namespace
@@ -420,10 +422,11 @@ int cvm_cv_predict_plan(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int
   if (const char *bad = predict_bad_shape(n_folds, max_fold_rows, ldX, K, M, A, dtype)) return fail(CVM_EINVAL, bad);
   const int esize = dtype == CVM_F64 ? 8 : 4;
   const void *where = aligned ? nullptr : reinterpret_cast<const void *>(8);      // (stands for every address)
-  const PredictPlan p = predict_plan(n_folds, max_fold_rows, K, M, A, esize, predict_vec(16 / esize, where, ldX, K, M, where, where, where));
-  info[0] = p.nt; info[1] = p.groups; info[2] = p.chunks; info[3] = p.total; info[4] = p.launches;
+  const TilePlan t = tile_plan(K, M, A, esize, tile_vec(16 / esize, where, ldX, K, M, where, where, where));
+  const PredictPlan p = predict_plan(n_folds, max_fold_rows, t.groups);
+  info[0] = t.nt; info[1] = t.groups; info[2] = p.chunks; info[3] = p.total; info[4] = p.launches;
   info[5] = p.total < PREDICT_MAX_WGS ? p.total : PREDICT_MAX_WGS;
-  info[6] = (int64_t)p.lds; info[7] = p.st_in_lds; info[8] = p.vec;
+  info[6] = (int64_t)t.lds; info[7] = t.st_in_lds; info[8] = t.vec;
   return CVM_OK;
 }
 

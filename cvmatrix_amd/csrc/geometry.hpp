@@ -13,6 +13,7 @@ constexpr int PITCH = 144;    // LDS row pitch of a panel, in elements (see bank
 constexpr int YT = 32;        // Y columns handled per diagonal work item (2 MFMA col tiles)
 constexpr int YPITCH = 48;    // LDS row pitch of the Y tile, in elements
 constexpr int NTHREADS = 512; // 8 waves, two per SIMD
+constexpr size_t LDS_BUDGET = 150 * 1024;   // of a CU's 160 KB: what the PLS fitter (pls.hpp) and the tiled product (tile_product.hpp) plan their dynamic LDS within
 constexpr int PANEL_ELEMS = STAGE_ROWS * PITCH;             // 2304
 constexpr int BUF_ELEMS = 2 * PANEL_ELEMS + STAGE_ROWS;     // A panel, B panel | Y tile, w
 constexpr int TARGET_WG_1 = 256;  // resident workgroups (both Gram kernels: one 8-wave workgroup per CU)

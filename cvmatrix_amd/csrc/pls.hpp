@@ -14,6 +14,7 @@
 // other's slices: the spin limit then reports status 1 instead of hanging; run one at a time.)
 // With S == 1 (many folds) the barrier is a __syncthreads().  All arithmetic in float64; fixed
 // summation orders, no float atomics: results do not depend on scheduling.
+// This file is the fitter alone; the validation errors of the fitted models are validation_sse.hpp's.
 //
 // Non-finite input.  A fold with a NaN or an infinity anywhere in its XTX or XTY is handed back as NaN
 // throughout (every component of B, W, P, Q, R) with n_fit -1, never as finite numbers: the stopping
@@ -27,7 +28,6 @@ constexpr int PLS_THREADS = 512;
 constexpr int PLS_NW = PLS_THREADS / 64;
 constexpr int PLS_MAXM = 64;        // responses (the M x M eigenproblem lives in LDS)
 constexpr int PLS_MAXA = 512;       // components
-constexpr size_t PLS_LDS_BUDGET = 150 * 1024;
 
 struct PlsArgs {
   const void *XTX, *XTY;            // [F][K][K], [F][K][M]
@@ -1080,8 +1080,8 @@ bool make_pls_plan(int64_t F, int K, int M, int A, int esize, int cus, PlsPlan &
     if (S > s_max && best) break;                              // more slices than s_max only if the LDS demands it
     const int rows = (K + S - 1) / S;
     if ((K + rows - 1) / rows != S) continue;                  // the same cut as a smaller S
-    if (pls_lds_bytes(K, M, A, rows, S > 1, 0, 0, 0, esize) > PLS_LDS_BUDGET) continue;
-    const bool res = pls_lds_bytes(K, M, A, rows, S > 1, 0, 0, 1, esize) <= PLS_LDS_BUDGET;
+    if (pls_lds_bytes(K, M, A, rows, S > 1, 0, 0, 0, esize) > LDS_BUDGET) continue;
+    const bool res = pls_lds_bytes(K, M, A, rows, S > 1, 0, 0, 1, esize) <= LDS_BUDGET;
     const double bytes = (double)rows * K * esize;
     const double t = bytes / (res ? PLS_LDS_BYTES_PER_US : PLS_CU_BYTES_PER_US) +
                      (S > 1 ? (M > 1 ? 4 : 3) * PLS_BARRIER_US : 0.0);
@@ -1093,9 +1093,9 @@ bool make_pls_plan(int64_t F, int K, int M, int A, int esize, int cus, PlsPlan &
   p.folds_per_launch = best == 1 ? (int)(Fe < (1 << 20) ? Fe : (1 << 20)) : cus / best;
   if (p.folds_per_launch < 1) return false;
   // what else stays in LDS, most valuable first: the slice of XTX, of the deflated XTY, of P and R
-  p.xres = pls_lds_bytes(K, M, A, p.rows, best > 1, 0, 0, 1, esize) <= PLS_LDS_BUDGET;
-  p.y_in_lds = pls_lds_bytes(K, M, A, p.rows, best > 1, 1, 0, p.xres, esize) <= PLS_LDS_BUDGET;
-  p.pr_in_lds = pls_lds_bytes(K, M, A, p.rows, best > 1, p.y_in_lds, 1, p.xres, esize) <= PLS_LDS_BUDGET;
+  p.xres = pls_lds_bytes(K, M, A, p.rows, best > 1, 0, 0, 1, esize) <= LDS_BUDGET;
+  p.y_in_lds = pls_lds_bytes(K, M, A, p.rows, best > 1, 1, 0, p.xres, esize) <= LDS_BUDGET;
+  p.pr_in_lds = pls_lds_bytes(K, M, A, p.rows, best > 1, p.y_in_lds, 1, p.xres, esize) <= LDS_BUDGET;
   p.lds = pls_lds_bytes(K, M, A, p.rows, best > 1, p.y_in_lds, p.pr_in_lds, p.xres, esize);
   return true;
 }
@@ -1122,13 +1122,13 @@ __global__ void pls_recovered_kernel(int32_t *status) {
 // The plan of the kernel that cannot wait for anybody: one workgroup per fold (S = 1).  False when a whole
 // fold's state does not fit the LDS budget (then a timed-out launch can only be poisoned).
 bool make_pls_plan_s1(int64_t F, int K, int M, int A, int esize, PlsPlan &p) {
-  if (pls_lds_bytes(K, M, A, K, 0, 0, 0, 0, esize) > PLS_LDS_BUDGET) return false;
+  if (pls_lds_bytes(K, M, A, K, 0, 0, 0, 0, esize) > LDS_BUDGET) return false;
   const int64_t Fe = F > 0 ? F : 1;
   p.S = 1; p.rows = K;
   p.folds_per_launch = (int)(Fe < (1 << 20) ? Fe : (1 << 20));
-  p.xres = pls_lds_bytes(K, M, A, K, 0, 0, 0, 1, esize) <= PLS_LDS_BUDGET;
-  p.y_in_lds = pls_lds_bytes(K, M, A, K, 0, 1, 0, p.xres, esize) <= PLS_LDS_BUDGET;
-  p.pr_in_lds = pls_lds_bytes(K, M, A, K, 0, p.y_in_lds, 1, p.xres, esize) <= PLS_LDS_BUDGET;
+  p.xres = pls_lds_bytes(K, M, A, K, 0, 0, 0, 1, esize) <= LDS_BUDGET;
+  p.y_in_lds = pls_lds_bytes(K, M, A, K, 0, 1, 0, p.xres, esize) <= LDS_BUDGET;
+  p.pr_in_lds = pls_lds_bytes(K, M, A, K, 0, p.y_in_lds, 1, p.xres, esize) <= LDS_BUDGET;
   p.lds = pls_lds_bytes(K, M, A, K, 0, p.y_in_lds, p.pr_in_lds, p.xres, esize);
   return true;
 }
@@ -1152,7 +1152,7 @@ bool make_pls_rep_plan(int64_t F, int K, int M, int A, int esize, int cus, PlsRe
   const int rows = (K + S - 1) / S;
   S = (K + rows - 1) / rows;
   const size_t lds = pls_rep_lds_bytes(K, M, A, rows);
-  if (lds > PLS_LDS_BUDGET) return false;
+  if (lds > LDS_BUDGET) return false;
   p.S = S; p.rows = rows; p.per_x = per_x; p.folds_per_launch = 8 * per_x; p.lds = lds;
   return true;
 }
@@ -1316,376 +1316,5 @@ int pls_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, int 
     HIP_OK(hipGetLastError());
   }
   if (p.S > 1) return pls_safety_net<T>(XTX, XTY, F, K, M, A, B, W, P, Q, R, n_fit, status, ws, st);
-  return CVM_OK;
-}
-
-// ----------------------------------------------------------------------------------
-// Validation errors of the folds' PLS models (round 3): the last step of a cross-validation on the
-// device.  For fold f, model with a + 1 components, response m:
-//   sse[f][a][m] = sum over the fold's validation rows i of
-//                  w_i ( ((x_i - muX_f) / sdX_f) . B[f][a][:, m] * sdY_f[m] + muY_f[m] - y_im )^2
-//   wsum[f]      = sum w_i
-// (centre / scale vectors are the fold stage's statistics outputs; a NULL one means 0 / 1).
-// One workgroup = 64 validation rows x 64 of the A M columns (a, m): the standardised rows and the
-// coefficient columns go through LDS 16 k at a time, wave w owns row tile w and four MFMA column
-// tiles; the squared errors are summed over the rows in a fixed order (registers -> lanes ->
-// waves -> a second small kernel over the row chunks: no float atomics).
-// ----------------------------------------------------------------------------------
-constexpr int SSE_ROWS = 64, SSE_KS = 16, SSE_ZP = 80, SSE_MAXNT = 6;   // (Z pitch 80: conflict-free MFMA operand reads)
-#ifdef CVM_STAMPS
-__device__ unsigned long long g_sse_stamps[8];
-#define SSE_STAMP(i) do { if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); g_sse_stamps[i] += now_ - sstamp_; sstamp_ = now_; } } while (0)
-#else
-#define SSE_STAMP(i)
-#endif
-struct SseArgs {
-  const void *X, *Y, *w, *muX, *sdX, *muY, *sdY, *B;
-  const int64_t *idx, *offs;
-  int K, M, A, n_chunks;        // n_chunks: row chunks of the longest fold
-  int st_in_lds;                // the fold's K means and reciprocal standard deviations fit in LDS next to the stages
-  double *part;                 // [F][n_chunks][A M] partial sums, [F][n_chunks] weight sums behind them
-  double *sse, *wsum;
-  int64_t F;
-};
-
-// Workgroup = 64 validation rows x W = 64 NT of the A M columns (a, m); wave w owns the 16 NT columns
-// from 16 NT w on, for all 64 rows: 4 x NT MFMA tiles, 4 A and NT B fragment reads per 4 NT MFMAs.
-// One workgroup per CU (the two LDS stages of B take most of it), one wave per SIMD: the matrix
-// pipe of a SIMD is never shared with another wave's vector arithmetic (a VALU instruction behind a
-// stream of float64 MFMAs of ANOTHER wave waits hundreds of cycles, tools/dma_vs_mfma.hip -- the
-// round-3 kernel, 64 x 64 tiles at several workgroups per CU, stood at 24 TFLOP/s), the next
-// stage's rows and coefficients are requested before the stage's MFMAs and written to the other
-// LDS buffer after them, one barrier per 16 k.  Rows are standardised on the way to LDS with the
-// reciprocal standard deviation (v_rcp + one Newton step: within 1 ulp of the division).
-// V: elements per global load (16 bytes' worth when K and M are multiples of that and the arrays are
-// aligned, else 1).  A vector-memory instruction costs the issuing wave hundreds of cycles on a busy CU
-// (tools/dma_issue.hip) and these waves also feed the matrix cores: 32 eight-byte loads per thread and
-// stage held the kernel at 25 TFLOP/s; with 16-byte loads and the statistics in LDS a stage takes 12.
-template <typename T, int NT, int V>
-__global__ __launch_bounds__(256) void pls_sse_kernel(const SseArgs a) {
-  constexpr int W = 64 * NT, BP = W + 16;                     // LDS pitch of B: conflict-free fragment reads
-#ifdef CVM_STAMPS
-  unsigned long long sstamp_ = __builtin_readcyclecounter();
-#endif
-  const int K = a.K, M = a.M, C = a.A * M;
-  const int chunk = blockIdx.x, cg = blockIdx.y, f = blockIdx.z;
-  const int64_t o0 = a.offs[f];
-  const int n = (int)(a.offs[f + 1] - o0);
-  const int r0 = chunk * SSE_ROWS;
-  double *part = a.part + ((size_t)f * a.n_chunks + chunk) * C;
-  double *wpart = a.part + (size_t)a.F * a.n_chunks * C + (size_t)f * a.n_chunks + chunk;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lk = lane >> 4, lc = lane & 15;
-  const int c0 = cg * W;
-  const int Cg = C - c0 < W ? C - c0 : W;                     // columns of this group
-  if (r0 >= n) {                                              // past this fold's rows: zeros
-    for (int c = tid; c < Cg; c += 256) part[c0 + c] = 0.0;
-    if (cg == 0 && tid == 0) *wpart = 0.0;
-    return;
-  }
-  extern __shared__ __attribute__((aligned(16))) unsigned char sse_smem[];
-  T *Zs = reinterpret_cast<T *>(sse_smem);                    // [2][KS][ZP], [k][row]: the A operand's lanes run over rows
-  T *Bs = Zs + 2 * SSE_KS * SSE_ZP;                           // [2][KS][BP], [k][column]
-  __shared__ int64_t rows[SSE_ROWS];
-  __shared__ double wl[SSE_ROWS];
-  const T *X = (const T *)a.X, *Y = (const T *)a.Y, *Wt = (const T *)a.w;
-  const T *muX = a.muX ? (const T *)a.muX + (size_t)f * K : nullptr;
-  const T *sdX = a.sdX ? (const T *)a.sdX + (size_t)f * K : nullptr;
-  const T *Bf = (const T *)a.B + (size_t)f * a.A * K * M;
-  if (tid < SSE_ROWS) {
-    const bool ok = r0 + tid < n;
-    const int64_t r = ok ? a.idx[o0 + r0 + tid] : 0;
-    rows[tid] = r;
-    wl[tid] = ok ? (Wt ? (double)Wt[r] : 1.0) : 0.0;
-  }
-  __syncthreads();
-  typedef typename MF<T>::acc_t acc_t;
-  acc_t acc[4][NT];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[rt][t] = (acc_t){0, 0, 0, 0};
-  // staging maps.  Z: thread -> (row zr = tid / 4, k quad zq = tid % 4): four CONSECUTIVE k of one
-  // row (a wave instruction touches 16 rows' lines once), 4 / V loads.  B: piece e = tid + 256 i of
-  // the stage's 16 x (W / V) pieces of V columns: k = e / (W / V), columns (e % (W / V)) V ...
-  // All loads are branch-free -- rows past the fold's end re-read row 0, k past K re-reads the
-  // last piece, columns past the group's end re-read column 0, and the values are zeroed in
-  // `store`: a per-thread branch around a load makes the compiler wait for everything in flight.
-  typedef T vec_t __attribute__((ext_vector_type(V)));
-  constexpr int ZL = 4 / V < 1 ? 1 : 4 / V;                   // Z loads per thread and stage
-  constexpr int ZV = 4 / ZL;                                  // elements per Z load (V, or 4 when V > 4 never happens)
-  static_assert(V == 1 || V == 2 || V == 4, "V is 1 or 16 bytes' worth");
-  constexpr int WP = W / V;                                   // pieces per k row
-  constexpr int NB = SSE_KS * WP / 256;                       // B loads per thread and stage
-  const int zr = tid >> 2, zq = tid & 3;
-  const bool zok = r0 + zr < n;
-  const T *xrow = X + rows[zr] * (int64_t)K;
-  const bool has_mu = muX != nullptr, has_sd = sdX != nullptr;
-  // statistics: (mean, 1 / sd) of all K columns in LDS when they fit, else read per stage
-  double *stl = reinterpret_cast<double *>(Bs + 2 * SSE_KS * BP);
-  const bool st_lds = a.st_in_lds != 0;
-  if (st_lds) {
-    for (int k = tid; k < K; k += 256) {
-      stl[2 * k] = has_mu ? (double)muX[k] : 0.0;
-      stl[2 * k + 1] = has_sd ? 1.0 / (double)sdX[k] : 1.0;
-    }
-  }
-  const T *mup = has_mu ? muX : xrow, *sdp = has_sd ? sdX : xrow;   // (absent statistics: a harmless second read of the row)
-  size_t boff[NB];
-  int blds[NB];
-  bool bok[NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int e = tid + 256 * i;
-    const int kk = e / WP, col = (e - kk * WP) * V;
-    bok[i] = c0 + col < C;                                    // (C is a multiple of V in the vector build)
-    const int gcol = bok[i] ? c0 + col : 0;
-    const int ba = gcol / M, bm = gcol - ba * M;
-    boff[i] = ((size_t)ba * K + kk) * M + bm;
-    blds[i] = kk * BP + col;
-  }
-  vec_t zv[ZL], zm[ZL], zs[ZL], bv[NB];
-  auto loadZ = [&](int j, int k0) {
-    const int k = k0 + 4 * zq + ZV * j;
-    const int kc = k < K ? k : K - ZV;
-    zv[j] = *reinterpret_cast<const vec_t *>(xrow + kc);
-    if (!st_lds) {
-      zm[j] = *reinterpret_cast<const vec_t *>(mup + kc);
-      zs[j] = *reinterpret_cast<const vec_t *>(sdp + kc);
-    }
-  };
-  auto loadB = [&](int i, int k0) {
-    // (k0 + kk < K except in the last stage: there the row K - 1 is re-read and zeroed in storeB)
-    const int kk = (tid + 256 * i) / WP;
-    const size_t ko = (size_t)(k0 + kk < K ? k0 : K - 1 - kk) * M;
-    bv[i] = *reinterpret_cast<const vec_t *>(Bf + boff[i] + ko);
-  };
-  auto storeZ = [&](int j, int k0, int buf) {
-    T *Zb = Zs + buf * SSE_KS * SSE_ZP;
-#pragma unroll
-    for (int e = 0; e < ZV; ++e) {
-      const int kq = 4 * zq + ZV * j + e, k = k0 + kq;
-      double mu, isd;
-      if (st_lds) {
-        const int kc = k < K ? k : K - 1;
-        mu = stl[2 * kc]; isd = stl[2 * kc + 1];
-      } else {
-        mu = has_mu ? (double)zm[j][e] : 0.0;
-        const double sd = has_sd ? (double)zs[j][e] : 1.0;
-        isd = __builtin_amdgcn_rcp(sd);
-        isd = fma(fma(-sd, isd, 1.0), isd, isd);
-      }
-      const T z = (T)(((double)zv[j][e] - mu) * isd);
-      Zb[kq * SSE_ZP + zr] = (zok && k < K) ? z : (T)0;
-    }
-  };
-  auto storeB = [&](int i, int k0, int buf) {
-    T *Bb = Bs + buf * SSE_KS * BP;
-    const int kk = (tid + 256 * i) / WP;
-    const bool ok = bok[i] && k0 + kk < K;
-    vec_t v = bv[i];
-#pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = ok ? v[e] : (T)0;
-    *reinterpret_cast<vec_t *>(Bb + blds[i]) = v;
-  };
-  // The next stage's requests and LDS writes are dealt out over the stage's 4 NT groups of four MFMAs
-  // ("steps"), one or two per step and pinned there: a vector-memory instruction takes its wave
-  // 150-450 cycles to issue on a busy CU and the matrix pipe runs dry behind a clump of them
-  // (tools/sse_stamps.py: 12 loads 2.0 k, arithmetic and LDS writes 1.9 k cycles per stage next to
-  // 6.8 k of MFMAs, one after the other).  Requests in the first half of the steps (rows first),
-  // writes in the second half (coefficients first, rows -- the longest latency -- last).
-  constexpr int STEPS = 4 * NT, NL = ZL + NB, NLS = (STEPS + 1) / 2, LPS = (NL + NLS - 1) / NLS;
-  constexpr int NSS = STEPS - NLS, SPS = (NL + NSS - 1) / NSS;
-  auto aux = [&](int step, int k1, int buf) {
-    if (step < NLS) {
-#pragma unroll
-      for (int q = 0; q < LPS; ++q) {
-        const int idx = step * LPS + q;
-        if (idx < ZL) loadZ(idx, k1);
-        else if (idx < NL) loadB(idx - ZL, k1);
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < SPS; ++q) {
-        const int idx = (step - NLS) * SPS + q;
-        if (idx < NB) storeB(idx, k1, buf);
-        else if (idx < NL) storeZ(idx - NB, k1, buf);
-      }
-    }
-  };
-  const int nst = (K + SSE_KS - 1) / SSE_KS;
-#pragma unroll
-  for (int j = 0; j < ZL; ++j) loadZ(j, 0);
-#pragma unroll
-  for (int i = 0; i < NB; ++i) loadB(i, 0);
-  if (st_lds) __syncthreads();                                // (stl)
-#pragma unroll
-  for (int i = 0; i < NB; ++i) storeB(i, 0, 0);
-#pragma unroll
-  for (int j = 0; j < ZL; ++j) storeZ(j, 0, 0);
-  __syncthreads();
-  SSE_STAMP(0);
-  // (narrow groups, NT < 3: several workgroups share a CU and hide each other's latencies; the
-  //  requests go first, the writes last, unpinned -- C = 20 at K = 4096 in float32: 0.95 ms against
-  //  1.6 ms with the pinned interleave)
-  constexpr bool PIN = NT >= 3;
-  for (int s = 0; s < nst; ++s) {
-    const bool more = s + 1 < nst;
-    const int k1 = (s + 1) * SSE_KS, nbuf = (s + 1) & 1;      // (that buffer was last read before the previous barrier)
-    const T *Zb = Zs + (s & 1) * SSE_KS * SSE_ZP, *Bb = Bs + (s & 1) * SSE_KS * BP;
-    if (!PIN && more) {
-#pragma unroll
-      for (int j = 0; j < ZL; ++j) loadZ(j, k1);
-#pragma unroll
-      for (int i = 0; i < NB; ++i) loadB(i, k1);
-    }
-#pragma unroll
-    for (int ks = 0; ks < SSE_KS; ks += 4) {
-      T af[4];
-#pragma unroll
-      for (int rt = 0; rt < 4; ++rt) af[rt] = Zb[(ks + lk) * SSE_ZP + 16 * rt + lc];
-      // (tiles past the group's last column multiply zeros: the four waves run side by side on
-      //  their SIMDs, skipping a tile in one of them would not shorten the stage)
-      T bf[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) bf[t] = Bb[(ks + lk) * BP + 16 * (wave * NT + t) + lc];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int rt = 0; rt < 4; ++rt) acc[rt][t] = MF<T>::mfma(af[rt], bf[t], acc[rt][t]);
-        if (PIN) {
-          if (more) aux((ks / 4) * NT + t, k1, nbuf);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    if (!PIN && more) {
-#pragma unroll
-      for (int i = 0; i < NB; ++i) storeB(i, k1, nbuf);
-#pragma unroll
-      for (int j = 0; j < ZL; ++j) storeZ(j, k1, nbuf);
-    }
-    SSE_STAMP(2);
-    __syncthreads();
-    SSE_STAMP(4);
-  }
-  // squared errors: register r of tile (rt, t) is (row 16 rt + drow(lane, r), column 16 (wave NT + t) + lc);
-  // summed over registers, row tiles, then the four lane groups -- a fixed order
-  const T *muY = a.muY ? (const T *)a.muY + (size_t)f * M : nullptr;
-  const T *sdY = a.sdY ? (const T *)a.sdY + (size_t)f * M : nullptr;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int lcol = 16 * (wave * NT + t) + lc;
-    const bool valid = lcol < Cg;
-    const int col = c0 + lcol;
-    const int m = valid ? col % M : 0;
-    const double sy = sdY ? (double)sdY[m] : 1.0, my = muY ? (double)muY[m] : 0.0;
-    double sacc = 0.0;
-#pragma unroll
-    for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int lr = 16 * rt + MF<T>::drow(lane, r);
-        if (valid && r0 + lr < n) {
-          const double e = (double)acc[rt][t][r] * sy + my - (double)Y[rows[lr] * (int64_t)M + m];
-          sacc += wl[lr] * (e * e);
-        }
-      }
-    const double s1 = __shfl(sacc, lc + 16), s2 = __shfl(sacc, lc + 32), s3 = __shfl(sacc, lc + 48);
-    const double sw = ((__shfl(sacc, lc) + s1) + s2) + s3;
-    if (lk == 0 && valid) part[col] = sw;
-  }
-  if (cg == 0 && tid == 0) {
-    double t = 0.0;
-    for (int i = 0; i < SSE_ROWS; ++i) t += wl[i];
-    *wpart = t;
-  }
-  SSE_STAMP(5);
-}
-
-// sums over a fold's row chunks, in chunk order
-__global__ void pls_sse_reduce_kernel(const SseArgs a) {
-  const int C = a.A * a.M;
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < a.F * C) {
-    const int64_t f = e / C;
-    const int c = (int)(e - f * C);
-    const int64_t n = a.offs[f + 1] - a.offs[f];
-    const int used = (int)((n + SSE_ROWS - 1) / SSE_ROWS);
-    double s = 0.0;
-    for (int ch = 0; ch < used; ++ch) s += a.part[((size_t)f * a.n_chunks + ch) * C + c];
-    a.sse[e] = s;
-  }
-  if (e < a.F) {
-    const int64_t n = a.offs[e + 1] - a.offs[e];
-    const int used = (int)((n + SSE_ROWS - 1) / SSE_ROWS);
-    double s = 0.0;
-    for (int ch = 0; ch < used; ++ch) s += a.part[(size_t)a.F * a.n_chunks * C + (size_t)e * a.n_chunks + ch];
-    a.wsum[e] = s;
-  }
-}
-
-size_t pls_sse_workspace_bytes(int64_t F, int64_t max_rows, int M, int A) {
-  const int64_t chunks = (max_rows + SSE_ROWS - 1) / SSE_ROWS;
-  return (size_t)F * (chunks > 0 ? chunks : 1) * ((size_t)A * M + 1) * 8 + 256;
-}
-
-template <typename T>
-int pls_sse_impl(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
-                 int64_t F, int64_t max_rows, int K, int M, int A, const void *muX, const void *sdX, const void *muY,
-                 const void *sdY, const void *B, double *sse, double *wsum, void *ws, size_t ws_bytes, hipStream_t st) {
-  if (ws_bytes < pls_sse_workspace_bytes(F, max_rows, M, A)) return fail(CVM_EWORKSPACE, "cvm_pls_validation_sse: workspace too small%s");
-  if (F == 0) return CVM_OK;
-  SseArgs a;
-  memset(&a, 0, sizeof(a));
-  a.X = X; a.Y = Y; a.w = w; a.muX = muX; a.sdX = sdX; a.muY = muY; a.sdY = sdY; a.B = B;
-  a.idx = idx; a.offs = offsets; a.K = K; a.M = M; a.A = A; a.F = F;
-  int64_t chunks = (max_rows + SSE_ROWS - 1) / SSE_ROWS;
-  if (chunks < 1) chunks = 1;
-  a.n_chunks = (int)chunks;
-  a.part = reinterpret_cast<double *>(ws);
-  a.sse = sse; a.wsum = wsum;
-  const int C = A * M;
-  if (F > 65535) return fail(CVM_EINVAL, "cvm_pls_validation_sse: at most 65535 folds per call%s");
-  // 16 NT columns per wave: as few column groups as possible (every group stages the rows again),
-  // then as little padding as possible
-  constexpr int VW = 16 / (int)sizeof(T);
-  const bool vec = K % VW == 0 && M % VW == 0 && K >= 4 && ((uintptr_t)X % 16 == 0) && ((uintptr_t)B % 16 == 0) &&
-                   (!muX || (uintptr_t)muX % 16 == 0) && (!sdX || (uintptr_t)sdX % 16 == 0);
-  // (float64 takes five column tiles per wave at most, four without 16-byte pieces: the wider variants of
-  //  those combinations spill -- 33 / 90 registers at six tiles, 3 at five scalar ones)
-  const int max_nt = sizeof(T) == 8 ? (vec ? 5 : 4) : SSE_MAXNT;
-  int nt = 1, best = 1 << 30;
-  for (int c = 1; c <= max_nt; ++c) {
-    const int groups = (C + 64 * c - 1) / (64 * c);
-    const int cost = groups * (4 * c + 1);
-    if (cost < best) { best = cost; nt = c; }
-  }
-  const unsigned groups = (unsigned)((C + 64 * nt - 1) / (64 * nt));
-  size_t lds = (size_t)2 * SSE_KS * (SSE_ZP + 64 * nt + 16) * sizeof(T);
-  // (statistics in LDS only where they do not cost residency: one workgroup per CU anyway, or a short K)
-  a.st_in_lds = (lds + (size_t)K * 16 + 2048 <= PLS_LDS_BUDGET && (lds > 80 * 1024 || K <= 512)) ? 1 : 0;
-  if (a.st_in_lds) lds += (size_t)K * 16;
-  void (*kern)(const SseArgs) = nullptr;
-#define CVM_SSE_PICK(N) kern = vec ? pls_sse_kernel<T, N, VW> : pls_sse_kernel<T, N, 1>
-  switch (nt) {
-    case 1: CVM_SSE_PICK(1); break;
-    case 2: CVM_SSE_PICK(2); break;
-    case 3: CVM_SSE_PICK(3); break;
-    case 4: CVM_SSE_PICK(4); break;
-    case 5:
-      if constexpr (sizeof(T) == 8) kern = pls_sse_kernel<T, 5, VW>;      // (vec only: see max_nt)
-      else CVM_SSE_PICK(5);
-      break;
-    default:
-      if constexpr (sizeof(T) == 4) CVM_SSE_PICK(6);
-      break;
-  }
-  if (!kern) return fail(CVM_EINVAL, "cvm_pls_validation_sse: no kernel for this shape%s");
-#undef CVM_SSE_PICK
-  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3((unsigned)chunks, groups, (unsigned)F), dim3(256), lds, st, a);
-  const int64_t ne = F * C > F ? F * C : F;
-  hipLaunchKernelGGL(pls_sse_reduce_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, a);
-  HIP_OK(hipGetLastError());
   return CVM_OK;
 }

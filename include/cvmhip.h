@@ -357,7 +357,9 @@ int cvm_cv_predict(const void *X, int64_t ldX, const int64_t *idx, const int64_t
  * are read in 16-byte pieces.  `aligned`: X, B, muX and sdX are 16-byte aligned.  The HIP runtime refuses a launch
  * of 2^32 threads or more in x, so a launch has at most 2^24 - 1 workgroups of 256 threads; the flat list of
  * workgroups is cut wherever that falls, inside a fold too: neither the number of folds nor the length of a fold is
- * limited by it (beyond 2^40 each, and 2^61 workgroups in all: CVM_EINVAL). */
+ * limited by it (beyond 2^40 each, and 2^61 workgroups in all: CVM_EINVAL).
+ * info[0], [1], [6], [7] and [8] are cvm_pls_validation_sse's choices too, for ldX = K: the two calls share the
+ * kernel variants and the rule that picks one. */
 int cvm_cv_predict_plan(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int K, int M, int A, int dtype,
                         int aligned, int64_t *info);
 /* info[0]=row slices per fold, [1]=rows per slice, [2]=folds per launch, [3]=1 if the slice of XTX

@@ -315,6 +315,75 @@ def test_validation_sse_on_the_device(pls, dtype, N, K, M, P, A, weighted, flags
     assert r.shape == (A, M) and bool(torch.isfinite(r).all())
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_validation_sse_reaches_every_variant(pls, dtype):
+    """Every instantiation of the scorer's kernel and both places of the fold's statistics, against the float64
+    torch formula of test_validation_sse_on_the_device with its tolerances (1e-10 / 2e-4 of the fold's largest
+    reference value): ragged folds of 1, 63, 64, 65 and 129 rows, weights, all four centring and scaling
+    flags, random coefficients (as tools/bench_predict.py draws them).  The 16-byte build with M = 4 and K a
+    multiple of 4, the scalar build with M = 3, odd K and copy=False; each at K about 20 (statistics in LDS)
+    and at K = 520 / 521 (statistics read per stage into registers under the narrow variants); A M one
+    value in each class of the cost rule.  The plan (cvm_cv_predict_plan with ldX = K is the scorer's plan
+    too) is asked first, and the grid must cover every (column tiles, 16-byte loads) pair that exists for the
+    element type and both places of the statistics: a change of the rule cannot leave a variant untested
+    unnoticed.
+    Worked out beforehand on the host (tests/predict_cases.emulate: z rounded to float32, one sequential
+    float32 accumulator; this design at K = 520 / 521 with A = 5, 95 and 127): at most 9.8e-7 of the fold's
+    largest reference value in float32, against the gate's 2e-4."""
+    import ctypes
+
+    import cvmatrix_amd as amd
+    from cvmatrix_amd import _lib
+    from cvmatrix_amd.pls import pls_validation_sse
+
+    f32 = dtype is np.float32
+    code = _lib.CVM_F32 if f32 else _lib.CVM_F64
+    sizes = (1, 63, 64, 65, 129)
+    N, F = sum(sizes), len(sizes)
+    builds = [(1, 4, (20, 520), (5, 25, 45, 62, 77) + ((95,) if f32 else ())),
+              (0, 3, (21, 521), (7, 33, 60, 83) + ((103, 127) if f32 else ()))]
+    lib = _lib.load()
+    reached, places = set(), set()
+    for vec, M, Ks, As in builds:
+        for K in Ks:
+            for A in As:
+                info = np.zeros(9, dtype=np.int64)
+                assert lib.cvm_cv_predict_plan(F, max(sizes), K, K, M, A, code, 1, ctypes.c_void_p(info.ctypes.data)) == _lib.CVM_OK
+                assert int(info[8]) == vec, (K, M, A)
+                reached.add((int(info[0]), vec))
+                places.add(int(info[7]))
+    exist = {(nt, 1) for nt in range(1, 7 if f32 else 6)} | {(nt, 0) for nt in range(1, 7 if f32 else 5)}
+    assert reached == exist and places == {0, 1}, (sorted(reached), sorted(places))
+
+    f64 = torch.float64
+    tol = 2e-4 if f32 else 1e-10
+    for vec, M, Ks, As in builds:
+        for K in Ks:
+            rng = np.random.default_rng(1000 * K + M)
+            X = (rng.standard_normal((N, K)) * rng.uniform(0.5, 2.0, K) + rng.standard_normal(K)).astype(dtype)
+            Y = (rng.standard_normal((N, M)) + 3).astype(dtype)
+            w = (rng.random(N) + 0.1).astype(dtype)
+            perm = rng.permutation(N).astype(np.int64)
+            folds = [perm[o:o + s].copy() for o, s in zip(np.cumsum((0,) + sizes[:-1]), sizes)]
+            cvm = amd.CVMatrix(True, True, True, True, dtype=dtype, copy=False)
+            cvm.fit(torch.from_numpy(X).cuda(), torch.from_numpy(Y).cuda(), torch.from_numpy(w).cuda())
+            batch = cvm.prepare_folds(folds)
+            _, stats = cvm.training_XTX_XTY_batched(batch)
+            muX, sdX, muY, sdY = (s.to(f64) for s in stats)
+            g = torch.Generator(device="cuda"); g.manual_seed(2)
+            for A in As:
+                B = torch.randn((F, A, K, M), dtype=cvm.X.dtype, device="cuda", generator=g) * 0.05
+                sse, wsum = pls_validation_sse(cvm, batch, stats, B)
+                for f, rows in enumerate(folds):
+                    val = torch.from_numpy(rows).to(B.device)
+                    pred = torch.matmul((cvm.X[val].to(f64) - muX[f]) / sdX[f], B[f].to(f64)) * sdY[f] + muY[f]
+                    wv = cvm.weights[val].to(f64)
+                    ref = ((pred - cvm.Y[val].to(f64)) ** 2 * wv).sum(dim=1)
+                    err, top = float((sse[f] - ref).abs().max()), float(ref.abs().max())
+                    assert err <= tol * top, (vec, K, A, f, f"{err / top:.2e} of the largest value")
+                    assert abs(float(wsum[f]) - float(wv.sum())) <= 1e-12 * float(wv.sum())
+
+
 def test_randomised_shapes_against_the_oracle():
     """tools/fuzz_pls.py: random N, K, M (1 ... 64), fold counts, components, element types, flags and
     weights -- the coefficients of every well-determined component against the NumPy oracle
