@@ -27,6 +27,7 @@ EXPORTS = (
     "cvm_gram_fit", "cvm_fold_workspace_bytes", "cvm_fold_update", "cvm_fold_update_ex", "cvm_plan_fold", "cvm_debug_force_splits", "cvm_debug_resident",
     "cvm_timing_enable", "cvm_timing_read", "cvm_timing_read_kinds", "cvm_fill_probe", "cvm_clock_probe",
     "cvm_sweep_workspace_bytes", "cvm_sweep_fit", "cvm_sweep_folds", "cvm_sweep_fold_range", "cvm_sweep_all",
+    "cvm_sweep_unions_workspace_bytes", "cvm_sweep_unions",
     "cvm_partition_workspace_bytes", "cvm_partition_labels", "cvm_partition_periodic", "cvm_weights_check",
     "cvm_pls_workspace_bytes", "cvm_pls_fit", "cvm_pls_plan",
     "cvm_pls_sse_workspace_bytes", "cvm_pls_validation_sse",
@@ -99,6 +100,11 @@ def load():
     lib.cvm_sweep_fold_range.restype = C.c_int
     lib.cvm_sweep_fold_range.argtypes = [vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, u32, dbl, dbl, C.c_int,
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, vp]
+    lib.cvm_sweep_unions_workspace_bytes.restype = sz
+    lib.cvm_sweep_unions_workspace_bytes.argtypes = [i64, C.c_int, C.c_int]
+    lib.cvm_sweep_unions.restype = C.c_int
+    lib.cvm_sweep_unions.argtypes = [vp, i64, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, u32, dbl, dbl, C.c_int,
+                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, vp, sz, vp]
     lib.cvm_partition_workspace_bytes.restype = sz
     lib.cvm_partition_workspace_bytes.argtypes = [i64, i64]
     lib.cvm_partition_labels.restype = C.c_int

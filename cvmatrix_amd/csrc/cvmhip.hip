@@ -42,6 +42,7 @@ namespace {
 #include "resident.hpp"
 #include "mid_tile.hpp"
 #include "host.hpp"
+#include "fold_unions.hpp"
 #include "partition.hpp"
 #include "pls.hpp"
 #include "ridge.hpp"
@@ -276,6 +277,54 @@ int cvm_sweep_folds(const int64_t *offsets, int64_t n_folds, int K, int M, int d
   return cvm_sweep_fold_range(offsets, n_folds, 0, n_folds, K, M, dtype, flags, ddof, resolution, weighted, G, H,
                               gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold, ws, ws_bytes,
                               splits, stream);
+}
+
+size_t cvm_sweep_unions_workspace_bytes(int64_t n_unions, int K, int M) {
+  if (n_unions < 0 || K <= 0 || M < 0) return 0;
+  return union_workspace_bytes(n_unions, K, M);
+}
+
+int cvm_sweep_unions(const int64_t *fold_offsets, int64_t n_total, const int64_t *union_folds,
+                     const int64_t *union_offsets, const int64_t *host_union_offsets, int64_t n_unions, int K, int M,
+                     int dtype, unsigned flags, double ddof, double resolution, int weighted, const void *G, const void *H,
+                     const double *gstats, void *out_XTX, void *out_XTY, void *out_muX, void *out_sdX, void *out_muY,
+                     void *out_sdY, double *out_fold, const void *sweep_ws, size_t sweep_ws_bytes, int64_t splits, void *ws,
+                     size_t ws_bytes, void *stream) {
+  // (everything below is decided before the device is touched)
+  if (n_unions < 0 || n_total <= 0 || K <= 0 || M < 0) return fail(CVM_EINVAL, "cvm_sweep_unions: bad shape%s");
+  if (dtype != CVM_F64 && dtype != CVM_F32) return fail(CVM_EINVAL, "cvm_sweep_unions: dtype must be CVM_F32 or CVM_F64%s");
+  if (!fold_offsets || !host_union_offsets || !G || !gstats || !sweep_ws)
+    return fail(CVM_EINVAL, "cvm_sweep_unions: null pointer%s");
+  if ((flags & CVM_RET_XTX) && !out_XTX) return fail(CVM_EINVAL, "cvm_sweep_unions: CVM_RET_XTX needs out_XTX%s");
+  if ((flags & CVM_RET_XTY) && (M == 0 || !H || !out_XTY))
+    return fail(CVM_EINVAL, "cvm_sweep_unions: CVM_RET_XTY needs Y, H and out_XTY%s");
+  const int s_off = (int)(splits & 0xfffff), s_diag = (int)((splits >> 20) & 0xfffff);
+  if (splits <= 0 || (splits >> 41) != 0 || s_off < 1 || s_diag < 1)
+    return fail(CVM_EINVAL, "cvm_sweep_unions: not a plan token of cvm_sweep_fit%s");
+  if (host_union_offsets[0] < 0) return fail(CVM_EINVAL, "cvm_sweep_unions: negative union offset%s");
+  for (int64_t u = 0; u < n_unions; ++u) {
+    const int64_t n = host_union_offsets[u + 1] - host_union_offsets[u];
+    if (n < 0) return fail(CVM_EINVAL, "cvm_sweep_unions: union offsets must be non-decreasing%s");
+    if (n == 0) return fail(CVM_EINVAL, "cvm_sweep_unions: a union of no fold%s");
+    if (n > n_total) return fail(CVM_EINVAL, "cvm_sweep_unions: a union of more folds than the sweep has%s");
+  }
+  if (n_unions > 0 && (!union_folds || !union_offsets || !ws)) return fail(CVM_EINVAL, "cvm_sweep_unions: null pointer%s");
+  const int esize = dtype == CVM_F64 ? 8 : 4;
+  const Geom g = make_geom(K, M, esize, 0);
+  const size_t stride = (size_t)(s_off > s_diag ? s_off : s_diag);
+  if ((size_t)n_total * stride * g.unit_bytes > sweep_ws_bytes)
+    return fail(CVM_EWORKSPACE, "cvm_sweep_unions: sweep workspace smaller than the one cvm_sweep_fit filled%s");
+  if (union_workspace_bytes(n_unions, K, M) > ws_bytes)
+    return fail(CVM_EWORKSPACE, "cvm_sweep_unions: workspace smaller than cvm_sweep_unions_workspace_bytes%s");
+  if (n_unions == 0) return CVM_OK;
+  const bool compacted = (splits >> 40) & 1;
+  if (dtype == CVM_F64)
+    return sweep_unions_impl<double>(fold_offsets, union_folds, union_offsets, n_unions, g, s_off, s_diag, compacted, flags,
+                                     ddof, resolution, weighted, G, H, gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY,
+                                     out_sdY, out_fold, sweep_ws, ws, (hipStream_t)stream);
+  return sweep_unions_impl<float>(fold_offsets, union_folds, union_offsets, n_unions, g, s_off, s_diag, compacted, flags,
+                                  ddof, resolution, weighted, G, H, gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY,
+                                  out_sdY, out_fold, sweep_ws, ws, (hipStream_t)stream);
 }
 
 size_t cvm_partition_workspace_bytes(int64_t N, int64_t n_labels) { return partition_workspace_bytes(N, n_labels); }

@@ -1492,6 +1492,114 @@ class CVMatrix:
         with ``None`` for statistics the flags do not ask for."""
         return self._training_matrices_batched(True, True, folds)
 
+    # ------------------------------------------------------------------ unions of folds (nested CV)
+    def _training_matrices_unions(self, rXTX: bool, rXTY: bool, folds, unions):
+        """The ``*_batched`` results for the complements of UNIONS of the folds: leading axis = union.  The
+        matrices are formed from the partials of one sweep over ``folds`` (cvm_sweep_unions: the full-data
+        matrices minus the sum of the folds' validation updates); no row of X is read again."""
+        from .unions import prepare_unions
+
+        if self._exchanges_globals():
+            raise NotImplementedError("unions of folds are not available while the full-data matrices are exchanged "
+                                      "between processes")
+        if self.X is None:
+            raise RuntimeError("call fit() first")
+        if rXTY and self.Y is None:
+            raise ValueError(MSG_NO_Y)
+        lib = _lib.load()
+        batch = self.prepare_folds(folds)
+        ub = prepare_unions(unions, batch.n_folds)
+        if self._sweep is None or self._sweep[0] is not batch:
+            # no sweep of this very batch at hand: the one-sweep fit for these folds, as fit(folds=...) runs it
+            # (it raises for folds that are not a partition, before anything of the current fit is touched)
+            if not batch.is_partition:
+                raise ValueError("fit(folds=...) needs folds that contain every row exactly once")
+            self._sweep_cache = None
+            self._ra = None
+            self._np_cache = {}
+            self._sum_w = None
+            with self._on_device():
+                neg = torch.empty(1, dtype=torch.int32, device=self.device)
+                self._fit_sweep(lib, batch, neg)
+                self._neg = neg
+            self._pending = False
+            self._after_globals()
+        batch, token = self._sweep
+        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
+        r_muX = cX or (rXTY and cY)                 # cvmatrix.py:828-831
+        r_muY = rXTY and (cX or cY)
+        r_sdX = sX
+        r_sdY = rXTY and sY
+        # the reference's data-dependent raises, on exact host counts, before anything is launched (_validate)
+        self._resolve_totals()
+        U = ub.n_unions
+        if (r_muX or r_muY or r_sdX or r_sdY) and U:
+            per_fold = batch.nz_val if self.weights is not None else batch.sizes
+            nz_val = np.add.reduceat(np.asarray(per_fold, dtype=np.int64)[ub.folds], ub.offsets[:-1])
+            if self.weights is not None:
+                nz_train = self._nz_total - nz_val
+                if np.any(nz_train == 0):
+                    raise ValueError(MSG_NZ_ZERO)
+            else:
+                nz_train = self._n_total - nz_val
+            if (r_sdX or r_sdY) and np.any(nz_train <= self.ddof):
+                raise ValueError(MSG_NZ_DDOF)
+        K, M = self._Kd, self._Md or 0
+        flags = ((_lib.RET_XTX if rXTX else 0) | (_lib.RET_XTY if rXTY else 0)
+                 | (_lib.CENTER_X if cX else 0) | (_lib.CENTER_Y if cY else 0)
+                 | (_lib.SCALE_X if sX else 0) | (_lib.SCALE_Y if sY else 0))
+        dev, dt = self.device, self._tdt
+        with self._on_device():
+            # fresh tensors (never the reuse_outputs arena: a nested loop keeps the pair matrices next to the folds')
+            out_XTX = torch.empty((U, K, K), dtype=dt, device=dev) if rXTX else None
+            out_XTY = torch.empty((U, K, M), dtype=dt, device=dev) if rXTY else None
+            stat = torch.empty(U * (2 * K + 2 * M), dtype=dt, device=dev)
+            muX, sdX = stat[:U * K].view(U, 1, K), stat[U * K:2 * U * K].view(U, 1, K)
+            muY = stat[2 * U * K:2 * U * K + U * M].view(U, 1, M) if M else None
+            sdY = stat[2 * U * K + U * M:].view(U, 1, M) if M else None
+            want = int(lib.cvm_sweep_unions_workspace_bytes(U, K, M))
+            ws = self.__dict__.get("_union_ws")
+            if ws is None or ws.numel() < want or ws.device != dev:
+                ws = self._union_ws = torch.empty(want, dtype=torch.uint8, device=dev)
+            ufolds, uoffs = ub.device(dev)
+            rc = _lib.CVM_OK if U == 0 else lib.cvm_sweep_unions(
+                batch.offsets.data_ptr(), batch.n_folds, ufolds.data_ptr(), uoffs.data_ptr(),
+                ub.offsets.ctypes.data, U, K, M, self._cdt, flags, float(self.ddof), float(self.resolution),
+                1 if self.weights is not None else 0,
+                self._G.data_ptr(), _lib.ptr(self._H), self._gs.data_ptr(),
+                _lib.ptr(out_XTX), _lib.ptr(out_XTY), muX.data_ptr(), sdX.data_ptr(), _lib.ptr(muY), _lib.ptr(sdY),
+                0, self._sweep_ws.data_ptr(), self._sweep_ws.numel(), token, ws.data_ptr(), ws.numel(),
+                self._stream(),
+            )
+            _lib.check(rc, "cvm_sweep_unions")
+        oXX, oXY, oX, oY = self._oXX, self._oXY, self._oX, self._oY
+        stats = (oX(muX) if r_muX else None, oX(sdX) if r_sdX else None,
+                 oY(muY) if r_muY else None, oY(sdY) if r_sdY else None)
+        if rXTX and rXTY:
+            return (oXX(out_XTX), oXY(out_XTY)), stats
+        return (oXX(out_XTX) if rXTX else oXY(out_XTY)), stats
+
+    def training_XTX_unions(self, folds, unions):
+        """``training_XTX_batched`` for the complements of unions of folds (not in the reference):
+        result u is ``training_XTX`` of the concatenated validation indices of the folds ``unions[u]``.
+
+        ``folds``: a ``Partitioner``, index arrays or a ``FoldBatch`` that PARTITIONS the rows; ``unions``: a
+        sequence of sequences of fold positions (in the batch's order; the order inside a union does not
+        matter), an ``(n, r)`` integer array, or ``unions.prepare_unions(...)``'s result.  ``ValueError`` for an
+        empty union, a repeated fold or a position out of range.  When the object's current sweep is not
+        of this very batch, the one-sweep fit for these folds runs first, exactly as
+        ``fit(X, Y, weights, folds=folds)`` runs it.  Results are fresh tensors."""
+        return self._training_matrices_unions(True, False, folds, unions)
+
+    def training_XTY_unions(self, folds, unions):
+        return self._training_matrices_unions(False, True, folds, unions)
+
+    def training_XTX_XTY_unions(self, folds, unions):
+        """``training_XTX_XTY_batched`` for the complements of unions of folds (see ``training_XTX_unions``):
+        ((XTX[U,K,K], XTY[U,K,M]), (muX[U,1,K], sdX[U,1,K], muY[U,1,M], sdY[U,1,M])) with ``None`` for
+        statistics the flags do not ask for.  Nested cross-validation: ``unions.fold_pairs(P)``."""
+        return self._training_matrices_unions(True, True, folds, unions)
+
     @staticmethod
     def _first(res):
         """Strip the fold axis of a one-fold batched result."""

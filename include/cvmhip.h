@@ -186,6 +186,37 @@ int cvm_sweep_fold_range(const int64_t *offsets, int64_t n_total, int64_t fold0,
                          void *out_sdX, void *out_muY, void *out_sdY, double *out_fold, void *ws, size_t ws_bytes,
                          int64_t splits, void *stream);
 
+/* Training matrices of the complements of UNIONS of folds of the sweep (nested cross-validation,
+ * repeated leave-several-groups-out): output u is what cvm_fold_update gives for the concatenated
+ * validation indices of the folds of union u (cvmatrix.py:754-896), formed from the partials the sweep
+ * left in sweep_ws as  G - sum_{f in S_u} U_f  -- no row of X is read again.
+ *   fold_offsets, n_total, weighted, sweep_ws, splits   as in cvm_sweep_fold_range; sweep_ws is only
+ *               read: the call may run any number of times after one sweep, between calls of
+ *               cvm_sweep_fold_range
+ *   union_folds        device int64[host_union_offsets[n_unions]]: union u owns
+ *                      union_folds[union_offsets[u] .. union_offsets[u+1]), fold numbers in
+ *                      [0, n_total), strictly ascending inside a union (the caller guarantees it)
+ *   union_offsets      device int64[n_unions+1]; host_union_offsets: the same array on the host
+ *   outputs            as in cvm_sweep_fold_range, leading axis = union;
+ *                      out_fold[u] = {sw_train, nz_train, sw_val, nz_val} of the union
+ *   ws                 this call's own scratch (cvm_sweep_unions_workspace_bytes): the unions'
+ *                      statistics vectors; what it held before does not matter
+ * The folds of a union are summed in ascending order, each fold's own ordered sum over its row splits
+ * first: the bits of a union's outputs depend on its folds, the partials and the token alone, and a
+ * union of one fold has the bits cvm_sweep_fold_range gives that fold.  No atomics.  CVM_EINVAL (bad
+ * token, missing pointer, n_unions < 0, negative / decreasing host_union_offsets, a union of no fold)
+ * and CVM_EWORKSPACE (ws or sweep_ws too short) are decided before the device is touched; n_unions == 0
+ * launches nothing. */
+size_t cvm_sweep_unions_workspace_bytes(int64_t n_unions, int K, int M);
+int cvm_sweep_unions(const int64_t *fold_offsets, int64_t n_total,
+                     const int64_t *union_folds, const int64_t *union_offsets,
+                     const int64_t *host_union_offsets, int64_t n_unions,
+                     int K, int M, int dtype, unsigned flags, double ddof, double resolution, int weighted,
+                     const void *G, const void *H, const double *gstats,
+                     void *out_XTX, void *out_XTY, void *out_muX, void *out_sdX, void *out_muY, void *out_sdY,
+                     double *out_fold, const void *sweep_ws, size_t sweep_ws_bytes, int64_t splits,
+                     void *ws, size_t ws_bytes, void *stream);
+
 /* Device-side Partitioner (replaces cvmatrix/partitioner.py:89-107 for integer labels):
  *   labels      int64[N], one fold label per row, each in [0, n_labels) (up to 4096 labels: one
  *               stable counting sort; more, e.g. leave-one-out with a label per row: the same
