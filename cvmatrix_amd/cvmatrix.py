@@ -27,6 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._request import fold_request, stat_addresses, stat_views
+from ._stage import dtype_code
 from .partitioner import Partitioner, partitioner_of, partitioner_pos
 
 MSG_NEG_W = "Weights must be non-negative."
@@ -170,7 +172,7 @@ class FoldBatch:
 class _ReadAhead:
     """State of a read-ahead over a Partitioner's folds (CVMatrix._ra_*)."""
     __slots__ = ("p", "arrs", "n", "batch", "key", "pos", "start", "count", "chunk", "max_chunk", "xtx", "xty",
-                 "stats", "need_stats", "need_std", "bad_zero", "bad_ddof", "sizes", "first", "lo", "hidx")
+                 "stats", "req", "bad_zero", "bad_ddof", "sizes", "first", "lo", "hidx")
 
 
 class CVMatrix:
@@ -298,7 +300,7 @@ class CVMatrix:
                 self._out_cast, npdt = "wide", np.dtype(np.float64)
                 self.output = "numpy"
         self._npdt, self._tdt = npdt, _TORCH_DT[npdt]
-        self._cdt = _lib.CVM_F64 if npdt == np.float64 else _lib.CVM_F32
+        self._cdt = dtype_code(self._tdt)
         self.resolution = np.finfo(self.dtype).resolution * 10  # cvmatrix.py:187
         self._device_arg = device
         self.device: Optional[torch.device] = None
@@ -401,6 +403,16 @@ class CVMatrix:
 
     def _oY(self, t, key=None):
         return self._cut(t, "Y", key)
+
+    @property
+    def _conv(self):
+        """The four converters in the order ``FoldRequest.pack`` takes them."""
+        return self._oXX, self._oXY, self._oX, self._oY
+
+    def _request(self, rXTX: bool, rXTY: bool):
+        """What a call asks for under the object's CURRENT centre / scale flags (public attributes: looked up
+        per call, never frozen)."""
+        return fold_request(rXTX, rXTY, self.center_X, self.center_Y, self.scale_X, self.scale_Y)
 
     def _device_dims(self, K: int, M: int):
         """Columns of the device copies of X and Y: padded with zero columns to rows of whole
@@ -1295,19 +1307,14 @@ class CVMatrix:
              stats_only: bool = False, sweep_fold: Optional[int] = None, sweep_all: bool = False):
         """One cvm_fold_update call over ``batch``.  Returns raw stacked device tensors.
         ``stats_only``: keep the return flags (they select which statistics the kernel
-        derives, cvmatrix.py:828-831) but produce no matrices.  ``sweep_all``: a lazy fit is
+        derives, _request.FoldRequest) but produce no matrices.  ``sweep_all``: a lazy fit is
         pending and ``batch`` partitions the rows -- the fit and the fold stage as one call
         (cvm_sweep_all)."""
         lib = _lib.load()
         if not sweep_all:
             self._ensure_fit()
         K, M, P = self._Kd, self._Md or 0, (batch.n_folds if sweep_fold is None else 1)
-        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
-        if stat_flags is not None:
-            cX, cY, sX, sY = stat_flags
-        flags = ((_lib.RET_XTX if rXTX else 0) | (_lib.RET_XTY if rXTY else 0)
-                 | (_lib.CENTER_X if cX else 0) | (_lib.CENTER_Y if cY else 0)
-                 | (_lib.SCALE_X if sX else 0) | (_lib.SCALE_Y if sY else 0))
+        flags = (self._request(rXTX, rXTY) if stat_flags is None else fold_request(rXTX, rXTY, *stat_flags)).flags
         dev, dt = self.device, self._tdt
         with self._on_device():
             mats = not stats_only
@@ -1319,10 +1326,7 @@ class CVMatrix:
                 out_XTX = torch.empty((P, K, K), dtype=dt, device=dev) if (rXTX and mats) else None
                 out_XTY = torch.empty((P, K, M), dtype=dt, device=dev) if (rXTY and mats) else None
                 # the four statistics: one allocation [muX | sdX | muY | sdY], each block [P, 1, *]
-                stat = torch.empty(P * (2 * K + 2 * M), dtype=dt, device=dev)
-                muX, sdX = stat[:P * K].view(P, 1, K), stat[P * K:2 * P * K].view(P, 1, K)
-                muY = stat[2 * P * K:2 * P * K + P * M].view(P, 1, M) if M else None
-                sdY = stat[2 * P * K + P * M:].view(P, 1, M) if M else None
+                muX, sdX, muY, sdY = stat_views(torch.empty(P * (2 * K + 2 * M), dtype=dt, device=dev), P, K, M)
                 neg_held = None
                 if self.reuse_outputs:
                     neg_held = torch.empty(1, dtype=torch.int32, device=dev)
@@ -1451,16 +1455,12 @@ class CVMatrix:
     def _finish(self, batch, rXTX: bool, rXTY: bool, sweep_fold: Optional[int] = None, sweep_all: bool = False):
         """Validity checks + the fold-stage launch for ``batch`` (or for fold ``sweep_fold`` of the
         batch the sweep served)."""
-        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
-        r_muX = cX or (rXTY and cY)                 # cvmatrix.py:828-831
-        r_muY = rXTY and (cX or cY)
-        r_sdX = sX
-        r_sdY = rXTY and sY
+        req = self._request(rXTX, rXTY)
         # the data-dependent raises come before anything is launched -- unless the counts they
         # need are still on their way from the other GPUs (multi-GPU, _totals_in_flight): then the
         # kernels are queued first (they never fault on such data) and the check, which has to
         # wait for the exchange anyway, follows; the results are only handed out after it
-        need_stats, need_std = r_muX or r_muY or r_sdX or r_sdY, r_sdX or r_sdY
+        need_stats, need_std = req.need_stats, req.need_std
         late = self._totals_in_flight()
         if late and self._passes_on_local_counts(batch, need_stats, need_std, only=sweep_fold):
             late = need_stats = False           # (decided on this process's own counts: nothing to wait for)
@@ -1471,12 +1471,7 @@ class CVMatrix:
         xtx, xty, (muX, sdX, muY, sdY), _ = self._run(batch, rXTX, rXTY, sweep_fold=sweep_fold, sweep_all=sweep_all)
         if late:
             self._validate(batch, need_stats, need_std, only=sweep_fold)
-        o, oXX, oXY, oX, oY = self._out, self._oXX, self._oXY, self._oX, self._oY
-        stats = (oX(muX) if r_muX else None, oX(sdX) if r_sdX else None,
-                 oY(muY) if r_muY else None, oY(sdY) if r_sdY else None)
-        if rXTX and rXTY:
-            return (oXX(xtx), oXY(xty)), stats
-        return (oXX(xtx) if rXTX else oXY(xty)), stats
+        return req.pack(xtx, xty, muX, sdX, muY, sdY, self._conv)
 
     # ------------------------------------------------------------------ public API
     def training_XTX_batched(self, folds):
@@ -1525,15 +1520,11 @@ class CVMatrix:
             self._pending = False
             self._after_globals()
         batch, token = self._sweep
-        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
-        r_muX = cX or (rXTY and cY)                 # cvmatrix.py:828-831
-        r_muY = rXTY and (cX or cY)
-        r_sdX = sX
-        r_sdY = rXTY and sY
+        req = self._request(rXTX, rXTY)
         # the reference's data-dependent raises, on exact host counts, before anything is launched (_validate)
         self._resolve_totals()
         U = ub.n_unions
-        if (r_muX or r_muY or r_sdX or r_sdY) and U:
+        if req.need_stats and U:
             per_fold = batch.nz_val if self.weights is not None else batch.sizes
             nz_val = np.add.reduceat(np.asarray(per_fold, dtype=np.int64)[ub.folds], ub.offsets[:-1])
             if self.weights is not None:
@@ -1542,21 +1533,15 @@ class CVMatrix:
                     raise ValueError(MSG_NZ_ZERO)
             else:
                 nz_train = self._n_total - nz_val
-            if (r_sdX or r_sdY) and np.any(nz_train <= self.ddof):
+            if req.need_std and np.any(nz_train <= self.ddof):
                 raise ValueError(MSG_NZ_DDOF)
         K, M = self._Kd, self._Md or 0
-        flags = ((_lib.RET_XTX if rXTX else 0) | (_lib.RET_XTY if rXTY else 0)
-                 | (_lib.CENTER_X if cX else 0) | (_lib.CENTER_Y if cY else 0)
-                 | (_lib.SCALE_X if sX else 0) | (_lib.SCALE_Y if sY else 0))
         dev, dt = self.device, self._tdt
         with self._on_device():
             # fresh tensors (never the reuse_outputs arena: a nested loop keeps the pair matrices next to the folds')
             out_XTX = torch.empty((U, K, K), dtype=dt, device=dev) if rXTX else None
             out_XTY = torch.empty((U, K, M), dtype=dt, device=dev) if rXTY else None
-            stat = torch.empty(U * (2 * K + 2 * M), dtype=dt, device=dev)
-            muX, sdX = stat[:U * K].view(U, 1, K), stat[U * K:2 * U * K].view(U, 1, K)
-            muY = stat[2 * U * K:2 * U * K + U * M].view(U, 1, M) if M else None
-            sdY = stat[2 * U * K + U * M:].view(U, 1, M) if M else None
+            muX, sdX, muY, sdY = stat_views(torch.empty(U * (2 * K + 2 * M), dtype=dt, device=dev), U, K, M)
             want = int(lib.cvm_sweep_unions_workspace_bytes(U, K, M))
             ws = self.__dict__.get("_union_ws")
             if ws is None or ws.numel() < want or ws.device != dev:
@@ -1564,7 +1549,7 @@ class CVMatrix:
             ufolds, uoffs = ub.device(dev)
             rc = _lib.CVM_OK if U == 0 else lib.cvm_sweep_unions(
                 batch.offsets.data_ptr(), batch.n_folds, ufolds.data_ptr(), uoffs.data_ptr(),
-                ub.offsets.ctypes.data, U, K, M, self._cdt, flags, float(self.ddof), float(self.resolution),
+                ub.offsets.ctypes.data, U, K, M, self._cdt, req.flags, float(self.ddof), float(self.resolution),
                 1 if self.weights is not None else 0,
                 self._G.data_ptr(), _lib.ptr(self._H), self._gs.data_ptr(),
                 _lib.ptr(out_XTX), _lib.ptr(out_XTY), muX.data_ptr(), sdX.data_ptr(), _lib.ptr(muY), _lib.ptr(sdY),
@@ -1572,12 +1557,7 @@ class CVMatrix:
                 self._stream(),
             )
             _lib.check(rc, "cvm_sweep_unions")
-        oXX, oXY, oX, oY = self._oXX, self._oXY, self._oX, self._oY
-        stats = (oX(muX) if r_muX else None, oX(sdX) if r_sdX else None,
-                 oY(muY) if r_muY else None, oY(sdY) if r_sdY else None)
-        if rXTX and rXTY:
-            return (oXX(out_XTX), oXY(out_XTY)), stats
-        return (oXX(out_XTX) if rXTX else oXY(out_XTY)), stats
+        return req.pack(out_XTX, out_XTY, muX, sdX, muY, sdY, self._conv)
 
     def training_XTX_unions(self, folds, unions):
         """``training_XTX_batched`` for the complements of unions of folds (not in the reference):
@@ -1743,26 +1723,23 @@ class CVMatrix:
         rXTX, rXTY = ra.key
         xtx, xty, (muX, sdX, muY, sdY), _ = self._run(sub, rXTX, rXTY)
         xtx, xty, (muX, sdX, muY, sdY) = self._own_results(xtx, xty, (muX, sdX, muY, sdY))
-        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
-        r_muX, r_muY, r_sdX, r_sdY = cX or (rXTY and cY), rXTY and (cX or cY), sX, rXTY and sY
+        ra.req = req = self._request(rXTX, rXTY)    # (what the chunk's calls return: as asked for when it was computed)
         c = self._cut_t                             # (padded device copies: cut the chunk once)
         ra.xtx = c(xtx, "XX").unbind(0) if xtx is not None else None
         ra.xty = c(xty, "XY").unbind(0) if xty is not None else None
-        ra.stats = (c(muX, "X").unbind(0) if r_muX else None, c(sdX, "X").unbind(0) if r_sdX else None,
-                    c(muY, "Y").unbind(0) if (r_muY and muY is not None) else None,
-                    c(sdY, "Y").unbind(0) if (r_sdY and sdY is not None) else None)
-        ra.need_stats, ra.need_std = bool(r_muX or r_muY or r_sdX or r_sdY), bool(r_sdX or r_sdY)
+        ra.stats = tuple(c(t, kind).unbind(0) if w else None
+                         for t, kind, w in zip((muX, sdX, muY, sdY), "XXYY", req.want))
         # the reference's raises (cvmatrix.py:612-630, 1074-1078), decided for the whole chunk
         ra.bad_zero = ra.bad_ddof = None
         self._resolve_weights_check()
-        if ra.need_stats:
+        if req.need_stats:
             self._resolve_totals()
             if self.weights is not None:
                 nz_train = self._nz_total - full.nz_val[a:b]
                 ra.bad_zero = (nz_train == 0).tolist()
             else:
                 nz_train = self._n_total - full.sizes[a:b]
-            if ra.need_std:
+            if req.need_std:
                 ra.bad_ddof = (nz_train <= self.ddof).tolist()
         # what the chunk was computed from: this stretch of the batch's private copy of the indices
         # (_ra_serve compares the caller's array with its fold's piece, exactly)
@@ -1784,19 +1761,13 @@ class CVMatrix:
         if n != ra.sizes[j] or (n == 1 and int(v[0]) != ra.first[j]) or (
                 n > 1 and not _same_indices(v, ra.hidx[ra.lo[j]:ra.lo[j + 1]])):
             return None                             # changed in place since the chunk was computed
-        if ra.need_stats:
+        if ra.req.need_stats:
             if ra.bad_zero is not None and ra.bad_zero[j]:
                 raise ValueError(MSG_NZ_ZERO)
             if ra.bad_ddof is not None and ra.bad_ddof[j]:
                 raise ValueError(MSG_NZ_DDOF)
         ra.pos += 1
-        o, oXX, oXY, oX, oY = self._out, self._oXX, self._oXY, self._oX, self._oY
-        st = ra.stats
-        stats = (None if st[0] is None else o(st[0][j]), None if st[1] is None else o(st[1][j]),
-                 None if st[2] is None else o(st[2][j]), None if st[3] is None else o(st[3][j]))
-        if ra.xtx is not None and ra.xty is not None:
-            return (o(ra.xtx[j]), o(ra.xty[j])), stats
-        return (o(ra.xtx[j]) if ra.xtx is not None else o(ra.xty[j])), stats
+        return ra.req.pack(ra.xtx, ra.xty, *ra.stats, (self._out,) * 4, at=j)
 
     def _one_small_fold(self, v: np.ndarray, rXTX: bool, rXTY: bool):
         """One fold of at most 32 rows given as an int64 index array -- the call of the reference's
@@ -1816,13 +1787,9 @@ class CVMatrix:
             raise IndexError(f"validation index out of bounds for {N} samples")
         if lo < 0:
             v = np.where(v < 0, v + N, v)
-        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
-        r_muX = cX or (rXTY and cY)                 # cvmatrix.py:828-831
-        r_muY = rXTY and (cX or cY)
-        r_sdX = sX
-        r_sdY = rXTY and sY
+        req = self._request(rXTX, rXTY)
         self._resolve_weights_check()
-        if r_muX or r_muY or r_sdX or r_sdY:        # the reference's raises, in its order (_validate)
+        if req.need_stats:                          # the reference's raises, in its order (_validate)
             self._resolve_totals()
             if self.weights is not None:
                 wh = self._host_weights()
@@ -1832,11 +1799,8 @@ class CVMatrix:
                     raise ValueError(MSG_NZ_ZERO)
             else:
                 nz_train = self._n_total - n
-            if (r_sdX or r_sdY) and nz_train <= self.ddof:
+            if req.need_std and nz_train <= self.ddof:
                 raise ValueError(MSG_NZ_DDOF)
-        flags = ((_lib.RET_XTX if rXTX else 0) | (_lib.RET_XTY if rXTY else 0)
-                 | (_lib.CENTER_X if cX else 0) | (_lib.CENTER_Y if cY else 0)
-                 | (_lib.SCALE_X if sX else 0) | (_lib.SCALE_Y if sY else 0) | _lib.IDX_HOST)
         dev, dt = self.device, self._tdt
         if torch.cuda.current_device() != dev.index:
             # (a model on another GPU than the caller's current one: the caller's device is restored)
@@ -1845,7 +1809,6 @@ class CVMatrix:
         xtx = torch.empty((K, K), dtype=dt, device=dev) if rXTX else None
         xty = torch.empty((K, M), dtype=dt, device=dev) if rXTY else None
         stat = torch.empty(2 * K + 2 * M, dtype=dt, device=dev)
-        base, es = stat.data_ptr(), stat.element_size()
         key = (K, M, self._cdt)
         if self._small_ws_key != key:
             self._small_ws_bytes = int(lib.cvm_fold_workspace_bytes(1, 32, 32, K, M, self._cdt, 0x3F))
@@ -1858,26 +1821,15 @@ class CVMatrix:
         off[1] = n
         rc = lib.cvm_fold_update(
             self.X.data_ptr(), _lib.ptr(self.Y), _lib.ptr(self.weights), v.ctypes.data, off.ctypes.data,
-            off.ctypes.data, 1, N, K, M, self._cdt, flags, float(self.ddof), float(self.resolution),
+            off.ctypes.data, 1, N, K, M, self._cdt, req.flags | _lib.IDX_HOST, float(self.ddof), float(self.resolution),
             self._G.data_ptr(), _lib.ptr(self._H), self._gs.data_ptr(), _lib.ptr(xtx), _lib.ptr(xty),
-            base, base + K * es, (base + 2 * K * es) if M else 0, (base + (2 * K + M) * es) if M else 0,
+            *stat_addresses(stat.data_ptr(), stat.element_size(), K, M),
             0, ws.data_ptr(), ws.numel(), self._stream(),
         )
         _lib.check(rc, "cvm_fold_update")
         if self.output == "numpy" or self._out_cast or K != self._Ku or M != (self._Mu or 0):
-            o, oXX, oXY, oX, oY = self._out, self._oXX, self._oXY, self._oX, self._oY
-            stats = (oX(stat[:K].view(1, K)) if r_muX else None, oX(stat[K:2 * K].view(1, K)) if r_sdX else None,
-                     oY(stat[2 * K:2 * K + M].view(1, M)) if r_muY else None,
-                     oY(stat[2 * K + M:].view(1, M)) if r_sdY else None)
-            if rXTX and rXTY:
-                return (oXX(xtx), oXY(xty)), stats
-            return (oXX(xtx) if rXTX else oXY(xty)), stats
-        stats = (stat[:K].view(1, K) if r_muX else None, stat[K:2 * K].view(1, K) if r_sdX else None,
-                 stat[2 * K:2 * K + M].view(1, M) if r_muY else None,
-                 stat[2 * K + M:].view(1, M) if r_sdY else None)
-        if rXTX and rXTY:
-            return (xtx, xty), stats
-        return (xtx if rXTX else xty), stats
+            return req.pack_one(xtx, xty, stat, K, M, self._conv)
+        return req.pack_one(xtx, xty, stat, K, M)       # (device results of the caller's shape: handed out as they are)
 
     def _finish_sweep_fold(self, i: int, rXTX: bool, rXTY: bool):
         """One fold of the sweep, finished on its own (cvm_sweep_fold_range): the short path of
@@ -1886,28 +1838,15 @@ class CVMatrix:
         lib = _lib.load()
         batch, token = self._sweep
         K, M = self._Kd, self._Md or 0
-        cX, cY, sX, sY = self.center_X, self.center_Y, self.scale_X, self.scale_Y
-        r_muX = cX or (rXTY and cY)                 # cvmatrix.py:828-831
-        r_muY = rXTY and (cX or cY)
-        r_sdX = sX
-        r_sdY = rXTY and sY
-        self._validate(batch, r_muX or r_muY or r_sdX or r_sdY, r_sdX or r_sdY, only=i)
+        req = self._request(rXTX, rXTY)
+        self._validate(batch, req.need_stats, req.need_std, only=i)
         cache = self._sweep_cache
         if cache is not None and cache["key"] == (rXTX, rXTY) and i in cache["left"]:
             cache["left"].discard(i)
-            xtx, xty = cache["xtx"], cache["xty"]
-            muX, sdX, muY, sdY = cache["stats"]
             if not cache["left"]:
                 self._sweep_cache = None
-            o = self._out                           # (the cache holds tensors already cut to K, M)
-            stats = (o(muX[i]) if r_muX else None, o(sdX[i]) if r_sdX else None,
-                     o(muY[i]) if r_muY else None, o(sdY[i]) if r_sdY else None)
-            if rXTX and rXTY:
-                return (o(xtx[i]), o(xty[i])), stats
-            return (o(xtx[i]) if rXTX else o(xty[i])), stats
-        flags = ((_lib.RET_XTX if rXTX else 0) | (_lib.RET_XTY if rXTY else 0)
-                 | (_lib.CENTER_X if cX else 0) | (_lib.CENTER_Y if cY else 0)
-                 | (_lib.SCALE_X if sX else 0) | (_lib.SCALE_Y if sY else 0))
+            # (the cache holds tensors already cut to K, M)
+            return req.pack(cache["xtx"], cache["xty"], *cache["stats"], (self._out,) * 4, at=i)
         dev, dt = self.device, self._tdt
         if torch.cuda.current_device() != dev.index:
             with torch.cuda.device(dev):
@@ -1915,24 +1854,15 @@ class CVMatrix:
         xtx = torch.empty((K, K), dtype=dt, device=dev) if rXTX else None
         xty = torch.empty((K, M), dtype=dt, device=dev) if rXTY else None
         stat = torch.empty(2 * K + 2 * M, dtype=dt, device=dev)
-        base, es = stat.data_ptr(), stat.element_size()
         rc = lib.cvm_sweep_fold_range(
-            batch.offsets.data_ptr(), batch.n_folds, i, 1, K, M, self._cdt, flags, float(self.ddof),
+            batch.offsets.data_ptr(), batch.n_folds, i, 1, K, M, self._cdt, req.flags, float(self.ddof),
             float(self.resolution), 1 if self.weights is not None else 0,
             self._G.data_ptr(), _lib.ptr(self._H), self._gs.data_ptr(),
-            _lib.ptr(xtx), _lib.ptr(xty), base, base + K * es,
-            (base + 2 * K * es) if M else 0, (base + (2 * K + M) * es) if M else 0, 0,
+            _lib.ptr(xtx), _lib.ptr(xty), *stat_addresses(stat.data_ptr(), stat.element_size(), K, M), 0,
             self._sweep_ws.data_ptr(), self._sweep_ws.numel(), token, self._stream(),
         )
         _lib.check(rc, "cvm_sweep_fold_range")
-        o, oXX, oXY, oX, oY = self._out, self._oXX, self._oXY, self._oX, self._oY
-        stats = (oX(stat[:K].view(1, K)) if r_muX else None,
-                 oX(stat[K:2 * K].view(1, K)) if r_sdX else None,
-                 oY(stat[2 * K:2 * K + M].view(1, M)) if r_muY else None,
-                 oY(stat[2 * K + M:].view(1, M)) if r_sdY else None)
-        if rXTX and rXTY:
-            return (oXX(xtx), oXY(xty)), stats
-        return (oXX(xtx) if rXTX else oXY(xty)), stats
+        return req.pack_one(xtx, xty, stat, K, M, self._conv)
 
     def training_XTX(self, validation_indices):
         """Training-set ``XᵀWX`` for every sample except ``validation_indices`` and
@@ -1961,12 +1891,12 @@ class CVMatrix:
             return None, None, None, None
         self._ensure_fit()
         self._validate(batch, True, r_sdX or r_sdY)
-        # the kernel derives "what to compute" from (return flags, centre/scale flags)
-        # exactly like cvmatrix.py:828-831; pass a flag set whose derived wants cover
-        # this method's own map (cvmatrix.py:570-573); surplus statistics are dropped
+        # the kernel derives "what to compute" from (return flags, centre/scale flags) by the rule of
+        # _request.FoldRequest; pass a flag set whose derived wants cover this method's own map
+        # (cvmatrix.py:570-573); surplus statistics are dropped
         _, _, (muX, sdX, muY, sdY), _ = self._run(
             batch, False, hasY, stat_flags=(r_muX, r_muY, r_sdX, r_sdY), stats_only=True)
-        o, oXX, oXY, oX, oY = self._out, self._oXX, self._oXY, self._oX, self._oY
+        oX, oY = self._oX, self._oY
         return (oX(muX) if r_muX else None, oX(sdX) if r_sdX else None,
                 oY(muY) if r_muY else None, oY(sdY) if r_sdY else None)
 

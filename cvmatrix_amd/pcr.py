@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._stage import dtype_code, launch, training_pair
 
 MAX_K = 512
 MAX_RESPONSES = 64
@@ -69,26 +70,7 @@ def pcr_fit_batched(XTX: torch.Tensor, XTY: Optional[torch.Tensor], A: int, *, r
     ``rank_tol`` (None: 32 K 2^-52): eigenvalues at or below ``rank_tol`` times the largest count as zero.
     ``check=False`` (the default) does not wait for the device.  ``check=True`` reads ``sweeps`` once and
     raises ``numpy.linalg.LinAlgError`` naming the first fold that did not converge."""
-    if not (isinstance(XTX, torch.Tensor) and XTX.is_cuda
-            and (XTY is None or (isinstance(XTY, torch.Tensor) and XTY.is_cuda))):
-        raise TypeError("pcr_fit_batched takes device tensors (the batched training matrices).")
-    if XTX.dim() == 2:
-        XTX = XTX.unsqueeze(0)
-        if XTY is not None:
-            XTY = XTY.unsqueeze(0) if XTY.dim() == 2 else XTY.reshape(1, -1, 1)
-    if XTX.dim() != 3 or XTX.shape[1] != XTX.shape[2]:
-        raise ValueError("XTX must be (F,K,K).")
-    if XTY is not None:
-        if XTY.dim() != 3 or XTY.shape[:2] != XTX.shape[:2]:
-            raise ValueError("XTX must be (F,K,K) and XTY (F,K,M).")
-        if XTX.dtype != XTY.dtype:
-            raise ValueError("XTX and XTY must both be float64 or both float32.")
-        if XTX.device != XTY.device:
-            raise ValueError("XTX and XTY must be on one device.")
-    if XTX.dtype not in (torch.float64, torch.float32):
-        raise ValueError("XTX and XTY must both be float64 or both float32.")
-    F, K = XTX.shape[:2]
-    M = 0 if XTY is None else XTY.shape[2]
+    XTX, XTY, F, K, M = training_pair("pcr_fit_batched", XTX, XTY, y_optional=True)
     if not 1 <= K <= MAX_K:
         raise ValueError(f"The device PCR takes 1 <= K <= {MAX_K}.")
     if XTY is not None and not 1 <= M <= MAX_RESPONSES:
@@ -96,33 +78,26 @@ def pcr_fit_batched(XTX: torch.Tensor, XTY: Optional[torch.Tensor], A: int, *, r
     A = check_components(A, K)
     tol = check_rank_tol(rank_tol)
     want_V = return_components or XTY is None
-    XTX = XTX.contiguous()
-    if XTY is not None:
-        XTY = XTY.contiguous()
-    lib = _lib.load()
     dev = XTX.device
-    code = _lib.CVM_F64 if XTX.dtype == torch.float64 else _lib.CVM_F32
-    with torch.cuda.device(dev):
-        one = lib.cvm_pcr_workspace_bytes(1, K, M, A)
-        nbytes = min(lib.cvm_pcr_workspace_bytes(F, K, M, A), max(one, WORKSPACE_LIMIT))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        B = None if XTY is None else torch.empty((F, A, K, M), dtype=XTX.dtype, device=dev)
-        eig = torch.empty((F, A), dtype=torch.float64, device=dev)
-        V = torch.empty((F, K, A), dtype=XTX.dtype, device=dev) if want_V else None
-        n_fit = torch.empty((F,), dtype=torch.int32, device=dev)
-        sweeps = torch.empty((F,), dtype=torch.int32, device=dev)
-        if F == 0:                # nothing to launch (and empty tensors have no address to hand over)
-            return PCRFit(B, eig, V, n_fit, sweeps)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.cvm_pcr_fit(_lib.ptr(XTX), _lib.ptr(XTY), F, K, M, A, code, tol, _lib.ptr(B), _lib.ptr(eig),
-                             _lib.ptr(V), _lib.ptr(n_fit), _lib.ptr(sweeps), _lib.ptr(ws), nbytes, stream)
-        _lib.check(rc, "cvm_pcr_fit")
-        ws.record_stream(torch.cuda.current_stream(dev))
-        if check:
-            host = sweeps.cpu().numpy()
-            bad = np.flatnonzero(host == -1)
-            if bad.size:
-                raise np.linalg.LinAlgError(
-                    f"pcr_fit_batched: fold {int(bad[0])} did not converge in {MAX_SWEEPS} Jacobi sweeps; "
-                    f"{bad.size} fold(s) failed.")
+    B = None if XTY is None else torch.empty((F, A, K, M), dtype=XTX.dtype, device=dev)
+    eig = torch.empty((F, A), dtype=torch.float64, device=dev)
+    V = torch.empty((F, K, A), dtype=XTX.dtype, device=dev) if want_V else None
+    n_fit = torch.empty((F,), dtype=torch.int32, device=dev)
+    sweeps = torch.empty((F,), dtype=torch.int32, device=dev)
+    if F == 0:                    # nothing to launch (and empty tensors have no address to hand over)
+        return PCRFit(B, eig, V, n_fit, sweeps)
+    lib = _lib.load()
+    launch("cvm_pcr_fit", dev,
+           lambda ws, nbytes, stream: lib.cvm_pcr_fit(
+               _lib.ptr(XTX), _lib.ptr(XTY), F, K, M, A, dtype_code(XTX.dtype), tol, _lib.ptr(B), _lib.ptr(eig),
+               _lib.ptr(V), _lib.ptr(n_fit), _lib.ptr(sweeps), ws, nbytes, stream),
+           lib.cvm_pcr_workspace_bytes(F, K, M, A), one=lib.cvm_pcr_workspace_bytes(1, K, M, A),
+           limit=WORKSPACE_LIMIT)
+    if check:
+        host = sweeps.cpu().numpy()
+        bad = np.flatnonzero(host == -1)
+        if bad.size:
+            raise np.linalg.LinAlgError(
+                f"pcr_fit_batched: fold {int(bad[0])} did not converge in {MAX_SWEEPS} Jacobi sweeps; "
+                f"{bad.size} fold(s) failed.")
     return PCRFit(B, eig, V, n_fit, sweeps)

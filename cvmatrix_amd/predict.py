@@ -16,28 +16,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._stage import dtype_code, launch, model_batch, stat_tensors
 
 MAX_RESPONSES = 64
 MAX_MODELS = 512
-
-
-def _code(dtype) -> int:
-    return _lib.CVM_F64 if dtype == torch.float64 else _lib.CVM_F32
-
-
-def _stat(name, t, F, width, dtype, dev):
-    """One statistics tensor as the kernel reads it: None, or F x width contiguous elements.  ``F`` None: one
-    model, shape (width,); else (F, width), or (F, 1, width) as the fold stage returns it.  The shape is checked,
-    not the element count alone: a (width, F) tensor would be read as (F, width) and predict wrongly in silence."""
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise TypeError(f"the {name} must be a device tensor or None.")
-    shapes = ((width,),) if F is None else ((F, width), (F, 1, width))
-    if t.dtype != dtype or t.device != dev or tuple(t.shape) not in shapes:
-        raise ValueError(f"the {name} does not belong to these folds / this model ({tuple(t.shape)} {t.dtype} on "
-                         f"{t.device}; wanted {' or '.join(str(x) for x in shapes)} {dtype} on {dev}).")
-    return t.contiguous()
 
 
 def _check_out(out, shape, dtype, dev):
@@ -71,29 +53,11 @@ def cv_predict(cvm, folds, stats, B: torch.Tensor, *, order: str = "rows",
         raise TypeError("cv_predict takes a device tensor of coefficients (F, A, K, M).")
     if order not in ("rows", "folds"):
         raise ValueError("order must be 'rows' or 'folds'.")
-    if cvm.X is None:
-        raise ValueError("cv_predict needs a fitted CVMatrix.")
-    if cvm.output != "torch" or cvm._out_cast:
-        raise ValueError("cv_predict takes device results of a float32 / float64 model "
-                         "(output='torch', no cast of the results).")
-    if B.dim() != 4:
-        raise ValueError("B must be (F, A, K, M).")
-    batch = cvm.prepare_folds(folds)
+    batch, B, (muX, sdX, muY, sdY), max_rows = model_batch("cv_predict", cvm, folds, stats, B)
     F, A, K, M = B.shape
-    if K != cvm.K or F != batch.n_folds:
-        raise ValueError("B does not belong to these folds / this model.")
     if not 1 <= M <= MAX_RESPONSES or not 1 <= A <= MAX_MODELS:
         raise ValueError(f"cv_predict takes 1..{MAX_RESPONSES} responses and 1..{MAX_MODELS} models per fold.")
-    dev = cvm.X.device
-    if B.dtype != cvm.X.dtype or B.device != dev or B.dtype not in (torch.float64, torch.float32):
-        raise ValueError(f"B is {B.dtype} on {B.device}, the model {cvm.X.dtype} on {dev}: cv_predict takes the "
-                         "coefficients of THIS model's training matrices.")
-    if len(stats) != 4:
-        raise ValueError("stats must be (muX, sdX, muY, sdY).")
-    muX = _stat("mean of X", stats[0], F, K, B.dtype, dev)
-    sdX = _stat("std of X", stats[1], F, K, B.dtype, dev)
-    muY = _stat("mean of Y", stats[2], F, M, B.dtype, dev)
-    sdY = _stat("std of Y", stats[3], F, M, B.dtype, dev)
+    dev = B.device
     n_idx = int(batch.host_offsets[-1])
     by_row = order == "rows"
     covered = True
@@ -107,18 +71,15 @@ def cv_predict(cvm, folds, stats, B: torch.Tensor, *, order: str = "rows",
         elif hidx is None:
             covered = n_idx == cvm.N          # (made on the device from labels: every row at most once)
     shape = (cvm.N if by_row else n_idx, A, M)
-    B = B.contiguous()
     lib = _lib.load()
-    max_rows = int(batch.sizes.max()) if batch.n_folds else 0
-    with torch.cuda.device(dev):
-        res = torch.empty(shape, dtype=B.dtype, device=dev) if out is None else _check_out(out, shape, B.dtype, dev)
-        if by_row and not covered:
-            res.fill_(float("nan"))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.cvm_cv_predict(_lib.ptr(cvm.X), cvm.X.stride(0), _lib.ptr(batch.idx), _lib.ptr(batch.offsets), F,
-                                max_rows, K, M, A, _code(B.dtype), _lib.ptr(muX), _lib.ptr(sdX), _lib.ptr(muY),
-                                _lib.ptr(sdY), _lib.ptr(B), _lib.ptr(res), 1 if by_row else 0, stream)
-        _lib.check(rc, "cvm_cv_predict")
+    res = torch.empty(shape, dtype=B.dtype, device=dev) if out is None else _check_out(out, shape, B.dtype, dev)
+    if by_row and not covered:
+        res.fill_(float("nan"))
+    launch("cvm_cv_predict", dev,
+           lambda _ws, _n, stream: lib.cvm_cv_predict(
+               _lib.ptr(cvm.X), cvm.X.stride(0), _lib.ptr(batch.idx), _lib.ptr(batch.offsets), F, max_rows, K, M, A,
+               dtype_code(B.dtype), _lib.ptr(muX), _lib.ptr(sdX), _lib.ptr(muY), _lib.ptr(sdY), _lib.ptr(B),
+               _lib.ptr(res), 1 if by_row else 0, stream))
     return res
 
 
@@ -144,24 +105,15 @@ def predict(X: torch.Tensor, B: torch.Tensor, stats=None) -> torch.Tensor:
     if (K > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < K):
         raise ValueError("X must have unit column stride and a row stride >= K.")
     dev = X.device
-    if stats is None:
-        stats = (None, None, None, None)
-    if len(stats) != 4:
-        raise ValueError("stats must be None or (muX, sdX, muY, sdY).")
-    muX = _stat("mean of X", stats[0], None, K, B.dtype, dev)
-    sdX = _stat("std of X", stats[1], None, K, B.dtype, dev)
-    muY = _stat("mean of Y", stats[2], None, M, B.dtype, dev)
-    sdY = _stat("std of Y", stats[3], None, M, B.dtype, dev)
+    muX, sdX, muY, sdY = stat_tensors((None,) * 4 if stats is None else stats, None, K, M, B.dtype, dev)
     B = B.contiguous()
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        res = torch.empty((n, A, M), dtype=B.dtype, device=dev)
-        if n == 0:
-            return res
-        offsets = torch.arange(0, n + 1, n, dtype=torch.int64, device=dev)      # {0, n}, made on the device: no copy to wait for
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.cvm_cv_predict(_lib.ptr(X), max(X.stride(0), K), 0, _lib.ptr(offsets), 1, n, K, M, A, _code(B.dtype),
-                                _lib.ptr(muX), _lib.ptr(sdX), _lib.ptr(muY), _lib.ptr(sdY), _lib.ptr(B), _lib.ptr(res),
-                                0, stream)
-        _lib.check(rc, "cvm_cv_predict")
+    res = torch.empty((n, A, M), dtype=B.dtype, device=dev)
+    if n == 0:
+        return res
+    offsets = torch.arange(0, n + 1, n, dtype=torch.int64, device=dev)      # {0, n}, made on the device: no copy to wait for
+    launch("cvm_cv_predict", dev,
+           lambda _ws, _n, stream: lib.cvm_cv_predict(
+               _lib.ptr(X), max(X.stride(0), K), 0, _lib.ptr(offsets), 1, n, K, M, A, dtype_code(B.dtype),
+               _lib.ptr(muX), _lib.ptr(sdX), _lib.ptr(muY), _lib.ptr(sdY), _lib.ptr(B), _lib.ptr(res), 0, stream))
     return res

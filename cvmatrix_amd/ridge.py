@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._stage import dtype_code, launch, training_pair
 
 MAX_K = 4096
 MAX_RESPONSES = 64
@@ -50,48 +51,31 @@ def ridge_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, lambdas, *, check: b
     ``check=False`` (the default) does not wait for the device.  ``check=True`` reads ``info`` once and
     raises ``numpy.linalg.LinAlgError`` naming the first (fold, lambda, pivot) whose matrix was not
     positive definite."""
-    if not (isinstance(XTX, torch.Tensor) and XTX.is_cuda and isinstance(XTY, torch.Tensor) and XTY.is_cuda):
-        raise TypeError("ridge_fit_batched takes device tensors (the batched training matrices).")
-    if XTX.dim() == 2:
-        XTX = XTX.unsqueeze(0)
-        XTY = XTY.unsqueeze(0) if XTY.dim() == 2 else XTY.reshape(1, -1, 1)
-    if XTX.dim() != 3 or XTY.dim() != 3 or XTX.shape[1] != XTX.shape[2] or XTY.shape[:2] != XTX.shape[:2]:
-        raise ValueError("XTX must be (F,K,K) and XTY (F,K,M).")
-    if XTX.dtype != XTY.dtype or XTX.dtype not in (torch.float64, torch.float32):
-        raise ValueError("XTX and XTY must both be float64 or both float32.")
-    if XTX.device != XTY.device:
-        raise ValueError("XTX and XTY must be on one device.")
-    F, K, M = XTY.shape
+    XTX, XTY, F, K, M = training_pair("ridge_fit_batched", XTX, XTY)
     if not 1 <= K <= MAX_K:
         raise ValueError(f"The device ridge takes 1 <= K <= {MAX_K}.")
     if not 1 <= M <= MAX_RESPONSES:
         raise ValueError(f"The device ridge takes 1 to {MAX_RESPONSES} responses.")
     lam = check_lambdas(lambdas)
     L = lam.size
-    XTX = XTX.contiguous()
-    XTY = XTY.contiguous()
-    lib = _lib.load()
     dev = XTX.device
-    code = _lib.CVM_F64 if XTX.dtype == torch.float64 else _lib.CVM_F32
-    with torch.cuda.device(dev):
-        one = lib.cvm_ridge_workspace_bytes(1, K, M, 1)
-        nbytes = min(lib.cvm_ridge_workspace_bytes(F, K, M, L), max(one, WORKSPACE_LIMIT))
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        B = torch.empty((F, L, K, M), dtype=XTX.dtype, device=dev)
-        info = torch.empty((F, L), dtype=torch.int32, device=dev)
-        if F == 0:                # nothing to launch (and empty tensors have no address to hand over)
-            return RidgeFit(B, info)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.cvm_ridge_fit(_lib.ptr(XTX), _lib.ptr(XTY), F, K, M, lam.ctypes.data, L, code, _lib.ptr(B),
-                               _lib.ptr(info), _lib.ptr(ws), nbytes, stream)
-        _lib.check(rc, "cvm_ridge_fit")
-        ws.record_stream(torch.cuda.current_stream(dev))
-        if check and F:
-            host = info.cpu().numpy()
-            bad = np.argwhere(host != 0)
-            if bad.size:
-                f, l = (int(v) for v in bad[0])
-                raise np.linalg.LinAlgError(
-                    f"ridge_fit_batched: fold {f}, lambda[{l}] = {lam[l]!r}: pivot {int(host[f, l])} is not "
-                    f"positive (XTX + lambda I is not positive definite); {len(bad)} problem(s) failed.")
+    B = torch.empty((F, L, K, M), dtype=XTX.dtype, device=dev)
+    info = torch.empty((F, L), dtype=torch.int32, device=dev)
+    if F == 0:                    # nothing to launch (and empty tensors have no address to hand over)
+        return RidgeFit(B, info)
+    lib = _lib.load()
+    launch("cvm_ridge_fit", dev,
+           lambda ws, nbytes, stream: lib.cvm_ridge_fit(
+               _lib.ptr(XTX), _lib.ptr(XTY), F, K, M, lam.ctypes.data, L, dtype_code(XTX.dtype), _lib.ptr(B),
+               _lib.ptr(info), ws, nbytes, stream),
+           lib.cvm_ridge_workspace_bytes(F, K, M, L), one=lib.cvm_ridge_workspace_bytes(1, K, M, 1),
+           limit=WORKSPACE_LIMIT)
+    if check:
+        host = info.cpu().numpy()
+        bad = np.argwhere(host != 0)
+        if bad.size:
+            f, l = (int(v) for v in bad[0])
+            raise np.linalg.LinAlgError(
+                f"ridge_fit_batched: fold {f}, lambda[{l}] = {lam[l]!r}: pivot {int(host[f, l])} is not "
+                f"positive (XTX + lambda I is not positive definite); {len(bad)} problem(s) failed.")
     return RidgeFit(B, info)

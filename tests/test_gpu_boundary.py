@@ -733,3 +733,72 @@ def test_backend_numpy_literal_runs_the_reference_call_sequence(amd):
         (ra, rb), rst = o.training_XTX_XTY(p.get_validation_indices(k))
         assert_normwise(a, ra, 1e-10, "XTX"); assert_normwise(b, rb, 1e-10, "XTY")
     assert isinstance(m.XTX, np.ndarray)
+
+
+@pytest.mark.serving
+def test_every_route_of_one_model_hands_out_the_batched_calls_bits(amd):
+    """One 40 x 6 x 2 float64 weighted problem through the four ways a result reaches the caller other than the
+    batched call -- the small-fold call, one fold of a sweep finished on its own, the read-ahead, unions of
+    one fold -- each compared bit for bit, matrices and statistics, with ``training_XTX_XTY_batched`` of the
+    same folds on a model in the same state.  The four routes share the request record, the carving of the
+    statistics block and the packing of the return value with the batched call; the arithmetic is the
+    library's, which decides per BATCH (longest fold, sweep or not) which kernels run, so every route is held
+    against the batched call that runs its kernels:
+
+    * 4 folds of 34, 2, 2 and 2 rows partition the rows.  A fold of at most 32 rows handed over as an index
+      array of its own takes ``_one_small_fold``: the same library call as the batched call of that one fold.
+    * ``_finish_sweep_fold`` serves a fold of MORE than 32 rows of a Partitioner whose sweep the model holds
+      (``fit(folds=...)``: 40 rows are never worth a sweep by themselves): the 34-row fold, against the batched
+      call of the four folds from the same sweep.  Unions of one fold come from that sweep too
+      (tests/test_gpu_unions.py asserts the same at its own shapes).
+    * The read-ahead starts only for a Partitioner of more than 16 folds: the same 40 rows as 40 folds of one
+      row (tests/test_gpu_boundary.py::test_per_fold_loop_over_many_folds_is_read_ahead compares the matrices
+      bit for bit at its shapes, the statistics to 1e-11; here both are compared exactly)."""
+    import torch
+
+    def same_bits(got, ref, i, what):
+        (gx, gy), gst = got
+        (rx, ry), rst = ref
+        assert torch.equal(gx, rx[i]) and torch.equal(gy, ry[i]), what
+        for g, r in zip(gst, rst):
+            assert g is not None and g.shape == r[i].shape and torch.equal(g, r[i]), what
+
+    rng = np.random.default_rng(406)
+    N, K, M = 40, 6, 2
+    X, Y, w = rng.random((N, K)), rng.random((N, M)), rng.random(N) + 0.1
+    labels = np.zeros(N, dtype=np.int64)
+    labels[rng.permutation(N)[:6]] = [1, 1, 2, 2, 3, 3]
+    p = amd.Partitioner(labels)
+    keys = list(p.folds_dict)
+    big = [k for k in keys if p.get_validation_indices(k).size == 34]
+    assert len(keys) == 4 and len(big) == 1
+
+    eager = amd.CVMatrix(lazy_fit=False)
+    eager.fit(X, Y, w)
+    m = amd.CVMatrix()
+    m.fit(X, Y, w)
+    for k in keys:
+        if k != big[0]:
+            v = p.get_validation_indices(k).copy()
+            same_bits(m.training_XTX_XTY(v), eager.training_XTX_XTY_batched([v]), 0, ("small fold", k))
+            assert m._sweep is None and m._ra is None
+
+    s = amd.CVMatrix()
+    s.fit(X, Y, w, folds=p)
+    ref = s.training_XTX_XTY_batched(p)
+    i = keys.index(big[0])
+    v = p.get_validation_indices(big[0])
+    assert s._sweep_fold_of(v) == i
+    same_bits(s.training_XTX_XTY(v), ref, i, "one fold of the sweep")
+    (ux, uy), ust = s.training_XTX_XTY_unions(p, [[f] for f in range(4)])
+    for f in range(4):
+        same_bits(((ux[f], uy[f]), tuple(t[f] for t in ust)), ref, f, ("union of one fold", f))
+
+    loo = amd.Partitioner(np.arange(N))
+    ref = eager.training_XTX_XTY_batched(loo)
+    r = amd.CVMatrix()
+    r.fit(X, Y, w)
+    for f, k in enumerate(loo.folds_dict):
+        got = r.training_XTX_XTY(loo.get_validation_indices(k))
+        assert r._ra is not None
+        same_bits(got, ref, f, ("read-ahead", f))

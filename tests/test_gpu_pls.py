@@ -168,6 +168,68 @@ def test_argument_errors(pls):
         pls.pls_fit_batched(XTX.cpu(), XTY.cpu(), 2)
 
 
+@pytest.mark.parametrize("factors", [False, True])
+def test_no_folds_give_empty_outputs_without_a_launch(pls, factors):
+    K, M, A = 6, 2, 3
+    XTX = torch.empty((0, K, K), dtype=torch.float64, device="cuda")
+    XTY = torch.empty((0, K, M), dtype=torch.float64, device="cuda")
+    pls.pls_fit_batched.last_status = None
+    fit = pls.pls_fit_batched(XTX, XTY, A, return_factors=factors)
+    assert fit.B.shape == (0, A, K, M) and fit.n_fit.shape == (0,) and fit.n_fit.dtype == torch.int32
+    assert pls.pls_fit_batched.last_status == 0
+    if factors:
+        assert fit.W.shape == fit.P.shape == fit.R.shape == (0, K, A) and fit.Q.shape == (0, M, A)
+    else:
+        assert fit.W is fit.P is fit.Q is fit.R is None
+
+
+def test_one_pair_of_matrices_is_one_fold(pls):
+    K, A = 5, 2
+    rng = np.random.default_rng(8)
+    X, y = rng.standard_normal((30, K)), rng.standard_normal(30)
+    XTX, XTy = torch.from_numpy(X.T @ X).cuda(), torch.from_numpy(X.T @ y).cuda()
+    fit = pls.pls_fit_batched(XTX, XTy, A)
+    assert fit.B.shape == (1, A, K, 1) and fit.n_fit.tolist() == [A]
+    assert torch.equal(fit.B, pls.pls_fit_batched(XTX[None], XTy.reshape(1, K, 1), A).B)
+
+
+def test_matrices_on_two_devices_are_refused(pls):
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one device")
+    XTX = torch.eye(4, dtype=torch.float64, device="cuda:0")[None]
+    XTY = torch.ones((1, 4, 2), dtype=torch.float64, device="cuda:1")
+    with pytest.raises(ValueError):
+        pls.pls_fit_batched(XTX, XTY, 2)
+
+
+@pytest.fixture(scope="module")
+def scored(pls):
+    """A fitted 24 x 4 x 2 model with 3 folds (F differs from both widths), its statistics and coefficients."""
+    import cvmatrix_amd as amd
+
+    X, Y, w, folds = fold_matrices(24, 4, 2, 3, 12)
+    cvm = amd.CVMatrix()
+    cvm.fit(X, Y, w)
+    batch = cvm.prepare_folds(folds)
+    (XTX, XTY), stats = cvm.training_XTX_XTY_batched(batch)
+    B = pls.pls_fit_batched(XTX, XTY, 2).B
+    return cvm, batch, stats, B, pls.pls_validation_sse(cvm, batch, stats, B)
+
+
+def test_validation_sse_checks_the_shape_of_the_statistics(pls, scored):
+    cvm, batch, stats, B, (sse, wsum) = scored
+    muX = stats[0]
+    assert muX.shape == (3, 1, 4)
+    with pytest.raises(ValueError):         # same element count, (K, F): would be read as (F, K)
+        pls.pls_validation_sse(cvm, batch, (muX.reshape(3, 4).t().contiguous(),) + stats[1:], B)
+    with pytest.raises(TypeError):
+        pls.pls_validation_sse(cvm, batch, (muX.cpu(),) + stats[1:], B)
+    flat = tuple(s.reshape(3, -1) for s in stats)
+    for st in (stats, flat):
+        sse2, wsum2 = pls.pls_validation_sse(cvm, batch, st, B)
+        assert torch.equal(sse2, sse) and torch.equal(wsum2, wsum)
+
+
 def test_end_to_end_equals_refitting_each_fold_with_sklearn(pls):
     """CVMatrix (centre + scale, ddof=1, unweighted) -> device PLS -> predictions on the validation
     rows, against scikit-learn refitted from scratch on every training set (PLS1: no inner
