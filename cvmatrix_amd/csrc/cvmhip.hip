@@ -47,6 +47,7 @@ namespace {
 #include "pls.hpp"
 #include "ridge.hpp"
 #include "pcr.hpp"
+#include "enet.hpp"
 #include "tile_product.hpp"
 #include "validation_sse.hpp"
 #include "predict.hpp"
@@ -412,6 +413,35 @@ int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int 
   if (dtype == CVM_F32)
     return ridge_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_ridge_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_enet_workspace_bytes(int64_t n_folds, int K, int M, int L) {
+  if (n_folds < 0 || K <= 0 || K > ENET_MAXK || M <= 0 || M > ENET_MAXM || L <= 0 || L > ENET_MAXL) return 0;
+  return enet_workspace_bytes(n_folds, K, M);
+}
+
+int cvm_enet_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
+                 double l1_ratio, double tol, int max_sweeps, int dtype, void *B, int32_t *info, int32_t *sweeps,
+                 void *ws, size_t ws_bytes, void *stream) {
+  if (!XTX || !XTY || !lambdas || !B || !info || !sweeps || !ws)
+    return fail(CVM_EINVAL, "cvm_enet_fit: null pointer%s");
+  if (n_folds < 0 || K <= 0 || K > ENET_MAXK || M <= 0 || M > ENET_MAXM)
+    return fail(CVM_EINVAL, "cvm_enet_fit: bad shape (1 <= K <= 4096, 1 <= M <= 64)%s");
+  if (L <= 0 || L > ENET_MAXL) return fail(CVM_EINVAL, "cvm_enet_fit: 1 <= L <= 256 penalties%s");
+  for (int l = 0; l < L; ++l)
+    if (!(lambdas[l] > 0.0) || lambdas[l] == HUGE_VAL)
+      return fail(CVM_EINVAL, "cvm_enet_fit: every penalty must be finite and > 0%s");
+  if (!(l1_ratio > 0.0 && l1_ratio <= 1.0))
+    return fail(CVM_EINVAL, "cvm_enet_fit: 0 < l1_ratio <= 1 (l1_ratio = 0 is cvm_ridge_fit)%s");
+  if (!(tol >= 1e-12 && tol < 1.0)) return fail(CVM_EINVAL, "cvm_enet_fit: 1e-12 <= tol < 1%s");
+  if (max_sweeps < 1) return fail(CVM_EINVAL, "cvm_enet_fit: max_sweeps >= 1%s");
+  if (dtype == CVM_F64)
+    return enet_fit_impl<double>(XTX, XTY, n_folds, K, M, lambdas, L, l1_ratio, tol, max_sweeps, B, info, sweeps, ws,
+                                 ws_bytes, (hipStream_t)stream);
+  if (dtype == CVM_F32)
+    return enet_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, l1_ratio, tol, max_sweeps, B, info, sweeps, ws,
+                                ws_bytes, (hipStream_t)stream);
+  return fail(CVM_EINVAL, "cvm_enet_fit: dtype must be CVM_F32 or CVM_F64%s");
 }
 
 size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A) {

@@ -353,6 +353,40 @@ size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A);
 int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
                 double rank_tol, void *B, double *eigenvalues, void *V, int32_t *n_fit, int32_t *sweeps,
                 void *ws, size_t ws_bytes, void *stream);
+/* Elastic net and lasso over a grid of penalties for every fold (the sparse member of the family; no
+ * counterpart in the reference): for fold f, response m and penalty l, with G = XTX[f], h = XTY[f][:, m],
+ *   B[f][l][:, m] = argmin over beta of
+ *                   1/2 beta' G beta - h' beta + lambdas[l] (l1_ratio |beta|_1 + 1/2 (1 - l1_ratio) |beta|_2^2)
+ * on the training matrices as they are.  For unweighted, centred data of n training rows this is scikit-learn's
+ * ElasticNet(alpha = lambda / n, l1_ratio, fit_intercept=False); with weights, the sum of weights in place of n.
+ * Cyclic coordinate descent with covariance updates, one wavefront per (fold, response): the penalties of a
+ * path are walked from the largest down, each warm-started from the one before; B is in the caller's order.
+ *   XTX, XTY, B, lambdas, ws   as cvm_ridge_fit has them, but every penalty finite and > 0
+ *   l1_ratio   0 < l1_ratio <= 1 (1: the lasso; 0 is cvm_ridge_fit)
+ *   tol        1e-12 <= tol < 1.  A problem is converged when, with g = h - G beta formed afresh and
+ *              r = g - lambda (1 - l1_ratio) beta, the largest over all K coordinates of
+ *                |r_j - lambda l1_ratio sign(beta_j)|      where beta_j != 0
+ *                max(0, |r_j| - lambda l1_ratio)           where beta_j == 0
+ *              is <= tol max_j |h_j|.  Nothing else counts as converged.
+ *   max_sweeps >= 1: passes over the coordinates plus certificate passes a problem may take
+ *   info   int32[n_folds][L][M]: 0 converged; 1 max_sweeps reached: B holds the last iterate, finite, and
+ *          sweeps == max_sweeps; 2 a value that is not finite met in the diagonal of G, in h, in a coefficient
+ *          or in the violation: B[f][l][:, m] is all NaN (never half-written), and the next penalty of that
+ *          path starts from zero.  A NaN in one response's column of XTY affects that response only.
+ *   sweeps int32[n_folds][L][M]: the passes taken (1 where lambda >= max|h| / l1_ratio: B is exactly zero)
+ *   ws     cvm_enet_workspace_bytes(n_folds, K, M, L) for min(n_folds M, 1024) paths in flight (host
+ *          arithmetic, no device query): one slot of K float64, 256-byte aligned, per path; any smaller
+ *          workspace that holds one slot runs fewer paths at a time with the same results to the bit.  Less
+ *          than one slot: CVM_EWORKSPACE.  Bad pointers, shapes, penalties, l1_ratio, tol, max_sweeps or
+ *          dtype: CVM_EINVAL.  n_folds == 0: nothing is launched.
+ * A coordinate whose denominator G_jj + lambda (1 - l1_ratio) is not > 0 stays at zero.  Arithmetic in float64
+ * for both dtypes (float32 inputs widened on load, B rounded once on store), no atomics, every sum and every
+ * admission to the active set in a fixed order: a path's bits depend on its own inputs and the penalty grid
+ * alone. */
+size_t cvm_enet_workspace_bytes(int64_t n_folds, int K, int M, int L);
+int cvm_enet_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
+                 double l1_ratio, double tol, int max_sweeps, int dtype, void *B, int32_t *info, int32_t *sweeps,
+                 void *ws, size_t ws_bytes, void *stream);
 /* Out-of-fold predictions of every fold's linear models, and predictions for new rows -- what the scorer
  * above forms and reduces to one number, stored whole (scikit-learn's cross_val_predict; no counterpart in
  * the reference, whose consumers predict fold by fold on the host): for fold f, row i of the fold, model a
