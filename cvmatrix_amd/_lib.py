@@ -34,6 +34,7 @@ EXPORTS = (
     "cvm_ridge_workspace_bytes", "cvm_ridge_fit",
     "cvm_pcr_workspace_bytes", "cvm_pcr_fit",
     "cvm_enet_workspace_bytes", "cvm_enet_fit",
+    "cvm_omp_workspace_bytes", "cvm_omp_fit",
     "cvm_cv_predict", "cvm_cv_predict_plan",
 )
 
@@ -139,6 +140,10 @@ def load():
     lib.cvm_enet_fit.restype = C.c_int
     lib.cvm_enet_fit.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, C.c_int, dbl, dbl, C.c_int, C.c_int, vp, vp, vp,
                                  vp, sz, vp]
+    lib.cvm_omp_workspace_bytes.restype = sz
+    lib.cvm_omp_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.cvm_omp_fit.restype = C.c_int
+    lib.cvm_omp_fit.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, dbl, C.c_int, vp, vp, vp, vp, sz, vp]
     lib.cvm_cv_predict.restype = C.c_int
     lib.cvm_cv_predict.argtypes = [vp, i64, vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int,
                                    vp, vp, vp, vp, vp, vp, C.c_int, vp]

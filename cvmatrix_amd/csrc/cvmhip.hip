@@ -48,6 +48,7 @@ namespace {
 #include "ridge.hpp"
 #include "pcr.hpp"
 #include "enet.hpp"
+#include "omp.hpp"
 #include "tile_product.hpp"
 #include "validation_sse.hpp"
 #include "predict.hpp"
@@ -442,6 +443,30 @@ int cvm_enet_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M
     return enet_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, l1_ratio, tol, max_sweeps, B, info, sweeps, ws,
                                 ws_bytes, (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_enet_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_omp_workspace_bytes(int64_t n_folds, int K, int M, int A) {
+  if (n_folds < 0 || K <= 0 || K > OMP_MAXK || M <= 0 || M > OMP_MAXM || A <= 0 || A > K || A > OMP_CAP) return 0;
+  return omp_workspace_bytes(n_folds, K, M);
+}
+
+int cvm_omp_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int normalize, double rank_tol,
+                int dtype, void *B, int32_t *support, int32_t *n_fit, void *ws, size_t ws_bytes, void *stream) {
+  // (everything below is decided before the device is touched)
+  if (!XTX || !XTY || !B || !support || !n_fit || !ws) return fail(CVM_EINVAL, "cvm_omp_fit: null pointer%s");
+  if (n_folds < 0 || K <= 0 || K > OMP_MAXK || M <= 0 || M > OMP_MAXM)
+    return fail(CVM_EINVAL, "cvm_omp_fit: bad shape (1 <= K <= 4096, 1 <= M <= 64)%s");
+  if (A <= 0 || A > K || A > OMP_CAP) return fail(CVM_EINVAL, "cvm_omp_fit: 1 <= A <= min(K, 64) selected variables%s");
+  if (normalize != 0 && normalize != 1) return fail(CVM_EINVAL, "cvm_omp_fit: normalize must be 0 or 1%s");
+  if (!(rank_tol < 1.0)) return fail(CVM_EINVAL, "cvm_omp_fit: rank_tol must be below 1 (<= 0: the default)%s");
+  if (rank_tol <= 0.0) rank_tol = 32.0 * A * 0x1p-52;
+  if (dtype == CVM_F64)
+    return omp_fit_impl<double>(XTX, XTY, n_folds, K, M, A, normalize, rank_tol, B, support, n_fit, ws, ws_bytes,
+                                (hipStream_t)stream);
+  if (dtype == CVM_F32)
+    return omp_fit_impl<float>(XTX, XTY, n_folds, K, M, A, normalize, rank_tol, B, support, n_fit, ws, ws_bytes,
+                               (hipStream_t)stream);
+  return fail(CVM_EINVAL, "cvm_omp_fit: dtype must be CVM_F32 or CVM_F64%s");
 }
 
 size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A) {

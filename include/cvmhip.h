@@ -387,6 +387,44 @@ size_t cvm_enet_workspace_bytes(int64_t n_folds, int K, int M, int L);
 int cvm_enet_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
                  double l1_ratio, double tol, int max_sweeps, int dtype, void *B, int32_t *info, int32_t *sweeps,
                  void *ws, size_t ws_bytes, void *stream);
+/* Orthogonal matching pursuit (greedy forward variable selection; scikit-learn's orthogonal_mp_gram; no
+ * counterpart in the reference) for every fold: for fold f and response m, with G = XTX[f], h = XTY[f][:, m]
+ * and S the ordered list of selected indices (empty at first), step a = 0 .. A - 1 is
+ *   1. alpha = h - G[:, S] gamma, gamma the least-squares coefficients on S (alpha = h while S is empty)
+ *   2. score_k = |alpha_k| (normalize == 0, scikit-learn's rule) or |alpha_k| / sqrt(G_kk) (normalize == 1, the
+ *      correlation with the residual; a column whose G_kk is not > 0 is never selected) for every k not in S
+ *   3. j = the index of the largest score; among equal scores the lowest index.  A largest score that is not
+ *      > 0 (no column may be selected, or every remaining alpha is exactly zero, as with h = 0) ends the path
+ *      with n_fit = a
+ *   4. the Cholesky factor L of G_SS gains the row w = L^-1 G[S, j] and the pivot d^2 = G_jj - w'w;
+ *      d^2 <= rank_tol G_jj ends the path with n_fit = a: the best remaining candidate depends on S
+ *   5. L L' gamma = h_S;  B[f][a][:, m] = gamma scattered to S, exactly 0 elsewhere.
+ * Each response selects its own variables.  One wavefront per (fold, response).
+ *   XTX, XTY   [n_folds][K][K] and [n_folds][K][M] in `dtype`, 1 <= K <= 4096, 1 <= M <= 64
+ *   A          steps = selected variables at most, 1 <= A <= min(K, 64)
+ *   normalize  0 or 1
+ *   rank_tol   below 1; <= 0: the default 32 A 2^-52
+ *   B          [n_folds][A][K][M] in `dtype`: for a >= n_fit[f][m], B[f][a][:, m] has the bits of
+ *              B[f][n_fit - 1][:, m] (all zeros if n_fit == 0), as cvm_pcr_fit pads
+ *   support    int32[n_folds][A][M]: the index selected at step a; -1 for a >= n_fit
+ *   n_fit      int32[n_folds][M]: 0 .. A, or -1 where a value that is not finite was met in the diagonal of G,
+ *              in h, in alpha or a score, in a pivot or in a coefficient: B[f][:][:, m] is then all NaN (written
+ *              once, after the status is known: never half-written) and support[f][:][m] all -1.  A NaN in one
+ *              response's column of XTY affects that response only, a NaN fold that fold only.
+ *   ws         cvm_omp_workspace_bytes(n_folds, K, M, A) for min(n_folds M, 1024) paths in flight (host
+ *              arithmetic, no device query): one slot of K float64, 256-byte aligned, per path; any smaller
+ *              workspace that holds one slot runs fewer paths at a time with the same results to the bit.  Less
+ *              than one slot: CVM_EWORKSPACE.  Bad pointers, shapes, A, normalize, rank_tol (NaN or >= 1) or
+ *              dtype: CVM_EINVAL, decided before the device is touched (cvm_omp_workspace_bytes: 0).
+ *              n_folds == 0: nothing is launched.
+ * Arithmetic in float64 for both dtypes (float32 inputs widened on load, which is exact: the selection on float32
+ * inputs is the float64 selection on those inputs; B rounded once on store), no atomics, every sum and every
+ * comparison in a fixed order: a path's bits depend on its own G, h, A, normalize and rank_tol alone, not on the
+ * batch around it, the workspace size or scheduling. */
+size_t cvm_omp_workspace_bytes(int64_t n_folds, int K, int M, int A);
+int cvm_omp_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int normalize,
+                double rank_tol, int dtype, void *B, int32_t *support, int32_t *n_fit,
+                void *ws, size_t ws_bytes, void *stream);
 /* Out-of-fold predictions of every fold's linear models, and predictions for new rows -- what the scorer
  * above forms and reduces to one number, stored whole (scikit-learn's cross_val_predict; no counterpart in
  * the reference, whose consumers predict fold by fold on the host): for fold f, row i of the fold, model a
