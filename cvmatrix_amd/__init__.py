@@ -11,3 +11,4 @@ __all__ = ["CVMatrix", "Partitioner", "FoldBatch"]
 
 from .partitioner import Partitioner
 from .cvmatrix import CVMatrix, FoldBatch
+from .streaming import StreamingCVMatrix  # noqa: E402,F401  (cvmatrix_amd.StreamingCVMatrix; __all__ stays the reference's names)

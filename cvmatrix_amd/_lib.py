@@ -21,6 +21,7 @@ CVM_F32, CVM_F64 = 0, 1
 RET_XTX, RET_XTY = 0x01, 0x02
 CENTER_X, CENTER_Y, SCALE_X, SCALE_Y = 0x04, 0x08, 0x10, 0x20
 IDX_HOST = 0x40
+STREAM_ACCUMULATOR, STREAM_SCRATCH, STREAM_CLOSE, STREAM_STATE_LEN = 0, 1, 2, 8
 
 EXPORTS = (
     "cvm_version", "cvm_source_hash", "cvm_last_error", "cvm_gstats_len", "cvm_fit_workspace_bytes",
@@ -28,6 +29,7 @@ EXPORTS = (
     "cvm_timing_enable", "cvm_timing_read", "cvm_timing_read_kinds", "cvm_fill_probe", "cvm_clock_probe",
     "cvm_sweep_workspace_bytes", "cvm_sweep_fit", "cvm_sweep_folds", "cvm_sweep_fold_range", "cvm_sweep_all",
     "cvm_sweep_unions_workspace_bytes", "cvm_sweep_unions",
+    "cvm_stream_workspace_bytes", "cvm_stream_reset", "cvm_stream_add", "cvm_stream_close", "cvm_timing_read_stream",
     "cvm_partition_workspace_bytes", "cvm_partition_labels", "cvm_partition_periodic", "cvm_weights_check",
     "cvm_pls_workspace_bytes", "cvm_pls_fit", "cvm_pls_plan",
     "cvm_pls_sse_workspace_bytes", "cvm_pls_validation_sse",
@@ -107,6 +109,17 @@ def load():
     lib.cvm_sweep_unions.restype = C.c_int
     lib.cvm_sweep_unions.argtypes = [vp, i64, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, u32, dbl, dbl, C.c_int,
                                      vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i64, vp, sz, vp]
+    lib.cvm_stream_workspace_bytes.restype = sz
+    lib.cvm_stream_workspace_bytes.argtypes = [C.c_int, i64, i64, C.c_int, C.c_int, C.c_int]
+    lib.cvm_stream_reset.restype = C.c_int
+    lib.cvm_stream_reset.argtypes = [vp, sz, i64, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.cvm_stream_add.restype = C.c_int
+    lib.cvm_stream_add.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp, sz, vp, vp, sz,
+                                   vp, vp]
+    lib.cvm_stream_close.restype = C.c_int
+    lib.cvm_stream_close.argtypes = [vp, sz, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.cvm_timing_read_stream.restype = C.c_int
+    lib.cvm_timing_read_stream.argtypes = [vp, vp, vp, vp]
     lib.cvm_partition_workspace_bytes.restype = sz
     lib.cvm_partition_workspace_bytes.argtypes = [i64, i64]
     lib.cvm_partition_labels.restype = C.c_int

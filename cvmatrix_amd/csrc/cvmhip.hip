@@ -43,6 +43,7 @@ namespace {
 #include "mid_tile.hpp"
 #include "host.hpp"
 #include "fold_unions.hpp"
+#include "stream_accumulate.hpp"
 #include "partition.hpp"
 #include "pls.hpp"
 #include "ridge.hpp"
@@ -329,6 +330,79 @@ int cvm_sweep_unions(const int64_t *fold_offsets, int64_t n_total, const int64_t
                                   out_sdY, out_fold, sweep_ws, ws, (hipStream_t)stream);
 }
 
+size_t cvm_stream_workspace_bytes(int what, int64_t n_folds, int64_t max_fold_rows, int K, int M, int dtype) {
+  if (n_folds <= 0 || max_fold_rows < 0 || K <= 0 || M < 0 || (dtype != CVM_F64 && dtype != CVM_F32)) return 0;
+  if (what == CVM_STREAM_ACCUMULATOR) return stream_units_bytes(n_folds, K, M, 8);
+  if (what == CVM_STREAM_SCRATCH) return stream_scratch_bytes(n_folds, max_fold_rows, K, M, dtype);
+  if (what == CVM_STREAM_CLOSE) return dtype == CVM_F64 ? 0 : stream_units_bytes(n_folds, K, M, 4);
+  return 0;
+}
+
+int cvm_stream_reset(void *acc, size_t acc_bytes, int64_t n_folds, int K, int M, int dtype, int64_t *state, void *stream) {
+  // (everything below is decided before the device is touched)
+  if (!acc || !state) return fail(CVM_EINVAL, "cvm_stream_reset: null pointer%s");
+  if (n_folds <= 0 || n_folds > 0x7fffffff || K <= 0 || M < 0) return fail(CVM_EINVAL, "cvm_stream_reset: bad shape%s");
+  if (dtype != CVM_F64 && dtype != CVM_F32) return fail(CVM_EINVAL, "cvm_stream_reset: dtype must be CVM_F32 or CVM_F64%s");
+  if ((uintptr_t)acc % 16) return fail(CVM_EINVAL, "cvm_stream_reset: the accumulator must be 16-byte aligned%s");
+  state[SS_MAGIC] = 0;
+  if (stream_units_bytes(n_folds, K, M, 8) > acc_bytes)
+    return fail(CVM_EWORKSPACE, "cvm_stream_reset: accumulator smaller than cvm_stream_workspace_bytes(CVM_STREAM_ACCUMULATOR)%s");
+  HIP_OK(hipMemsetAsync(acc, 0, stream_units_bytes(n_folds, K, M, 8), (hipStream_t)stream));
+  state[SS_FOLDS] = n_folds; state[SS_K] = K; state[SS_M] = M; state[SS_DTYPE] = dtype;
+  state[SS_CHUNKS] = 0; state[SS_ROWS] = 0; state[SS_WEIGHTED] = -1;
+  state[SS_MAGIC] = STREAM_MAGIC;
+  return CVM_OK;
+}
+
+int cvm_stream_add(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
+                   const int64_t *host_offsets, int64_t n_folds, int64_t n_rows, int K, int M, int dtype, void *acc,
+                   size_t acc_bytes, int64_t *state, void *ws, size_t ws_bytes, void *stream, int64_t *info) {
+  // (everything below is decided before the device is touched)
+  if (n_folds <= 0 || n_rows < 0 || K <= 0 || M < 0) return fail(CVM_EINVAL, "cvm_stream_add: bad shape%s");
+  if (dtype != CVM_F64 && dtype != CVM_F32) return fail(CVM_EINVAL, "cvm_stream_add: dtype must be CVM_F32 or CVM_F64%s");
+  if (const char *bad = stream_bad_state(state, n_folds, K, M, dtype)) return fail(CVM_EINVAL, bad);
+  if (!acc || !host_offsets) return fail(CVM_EINVAL, "cvm_stream_add: null pointer%s");
+  if (host_offsets[0] < 0) return fail(CVM_EINVAL, "cvm_stream_add: negative offset%s");
+  for (int64_t f = 0; f < n_folds; ++f)
+    if (host_offsets[f + 1] < host_offsets[f]) return fail(CVM_EINVAL, "cvm_stream_add: offsets must be non-decreasing%s");
+  if (host_offsets[n_folds] - host_offsets[0] != n_rows)
+    return fail(CVM_EINVAL, "cvm_stream_add: the folds must cover each of the chunk's n_rows rows exactly once%s");
+  if (stream_units_bytes(n_folds, K, M, 8) > acc_bytes)
+    return fail(CVM_EWORKSPACE, "cvm_stream_add: accumulator smaller than cvm_stream_workspace_bytes(CVM_STREAM_ACCUMULATOR)%s");
+  if (info) { info[0] = 0; info[1] = 0; }
+  if (n_rows == 0) return CVM_OK;                    // an empty chunk: nothing is launched
+  if (!X || !idx || !offsets || !ws) return fail(CVM_EINVAL, "cvm_stream_add: null pointer%s");
+  if ((M > 0) != (Y != nullptr)) return fail(CVM_EINVAL, "cvm_stream_add: Y goes with M > 0, and only with it%s");
+  if (state[SS_WEIGHTED] >= 0 && state[SS_WEIGHTED] != (w != nullptr))
+    return fail(CVM_EINVAL, "cvm_stream_add: every chunk of a stream has weights, or none has%s");
+  // (a workspace too small for one slot per fold: CVM_EWORKSPACE from the plan, before the first launch)
+  if (dtype == CVM_F64)
+    return stream_add_impl<double>(X, Y, w, idx, offsets, host_offsets, n_folds, n_rows, K, M, dtype, acc, state, ws,
+                                   ws_bytes, (hipStream_t)stream, info);
+  return stream_add_impl<float>(X, Y, w, idx, offsets, host_offsets, n_folds, n_rows, K, M, dtype, acc, state, ws, ws_bytes,
+                                (hipStream_t)stream, info);
+}
+
+int cvm_stream_close(void *acc, size_t acc_bytes, const int64_t *state, int64_t n_folds, int K, int M, int dtype, void *G,
+                     void *H, double *gstats, int32_t *neg_flag, void *ws, size_t ws_bytes, void *stream, void **units_out,
+                     size_t *units_bytes_out, int64_t *splits_out) {
+  // (everything below is decided before the device is touched)
+  if (n_folds <= 0 || K <= 0 || M < 0) return fail(CVM_EINVAL, "cvm_stream_close: bad shape%s");
+  if (dtype != CVM_F64 && dtype != CVM_F32) return fail(CVM_EINVAL, "cvm_stream_close: dtype must be CVM_F32 or CVM_F64%s");
+  if (const char *bad = stream_bad_state(state, n_folds, K, M, dtype)) return fail(CVM_EINVAL, bad);
+  if (!acc || !G || !gstats || (M > 0 && !H) || (dtype == CVM_F32 && !ws))
+    return fail(CVM_EINVAL, "cvm_stream_close: null pointer%s");
+  if (stream_units_bytes(n_folds, K, M, 8) > acc_bytes)
+    return fail(CVM_EWORKSPACE, "cvm_stream_close: accumulator smaller than cvm_stream_workspace_bytes(CVM_STREAM_ACCUMULATOR)%s");
+  if (dtype == CVM_F32 && stream_units_bytes(n_folds, K, M, 4) > ws_bytes)
+    return fail(CVM_EWORKSPACE, "cvm_stream_close: workspace smaller than cvm_stream_workspace_bytes(CVM_STREAM_CLOSE)%s");
+  if (units_bytes_out) *units_bytes_out = dtype == CVM_F64 ? stream_units_bytes(n_folds, K, M, 8) : stream_units_bytes(n_folds, K, M, 4);
+  if (splits_out) *splits_out = (int64_t)1 | ((int64_t)1 << 20);      // one slot per fold
+  if (dtype == CVM_F64)
+    return stream_close_impl<double>(acc, n_folds, K, M, G, H, gstats, neg_flag, ws, (hipStream_t)stream, units_out);
+  return stream_close_impl<float>(acc, n_folds, K, M, G, H, gstats, neg_flag, ws, (hipStream_t)stream, units_out);
+}
+
 size_t cvm_partition_workspace_bytes(int64_t N, int64_t n_labels) { return partition_workspace_bytes(N, n_labels); }
 
 int cvm_partition_labels(const int64_t *labels, int64_t N, int64_t n_labels, int64_t *idx_out,
@@ -555,23 +629,23 @@ int cvm_timing_enable(int on) {
   return CVM_OK;
 }
 
-static int timing_collect(double *ms, int64_t *n) {      // ms[4], n[4] by kind; resets the list
+static int timing_collect(double *ms, int64_t *n) {      // ms[N_KINDS], n[N_KINDS] by kind; resets the list
   std::lock_guard<std::mutex> lk(g_timing_mu);
-  for (int k = 0; k < 4; ++k) { ms[k] = 0; n[k] = 0; }
+  for (int k = 0; k < N_KINDS; ++k) { ms[k] = 0; n[k] = 0; }
   for (int i = 0; i < g_ntimed; ++i) {
     HIP_OK(hipEventSynchronize(g_timed[i].b));
     float t = 0;
     HIP_OK(hipEventElapsedTime(&t, g_timed[i].a, g_timed[i].b));
     const int k = g_timed[i].kind;
-    if (k >= 0 && k < 4) { ms[k] += t; ++n[k]; }
+    if (k >= 0 && k < N_KINDS) { ms[k] += t; ++n[k]; }
   }
   g_ntimed = 0;
   return CVM_OK;
 }
 
 int cvm_timing_read(double *ms_fit, int64_t *n_fit, double *ms_fold, int64_t *n_fold) {
-  double ms[4];
-  int64_t n[4];
+  double ms[N_KINDS];
+  int64_t n[N_KINDS];
   const int rc = timing_collect(ms, n);
   if (rc != CVM_OK) return rc;
   if (ms_fit) *ms_fit = ms[0];
@@ -583,7 +657,23 @@ int cvm_timing_read(double *ms_fit, int64_t *n_fit, double *ms_fold, int64_t *n_
 
 int cvm_timing_read_kinds(double *ms4, int64_t *n4) {
   if (!ms4 || !n4) return fail(CVM_EINVAL, "cvm_timing_read_kinds: null pointer%s");
-  return timing_collect(ms4, n4);
+  double ms[N_KINDS];
+  int64_t n[N_KINDS];
+  const int rc = timing_collect(ms, n);
+  for (int k = 0; k < 4; ++k) { ms4[k] = ms[k]; n4[k] = n[k]; }
+  return rc;
+}
+
+int cvm_timing_read_stream(double *ms_gram, int64_t *n_gram, double *ms_acc, int64_t *n_acc) {
+  double ms[N_KINDS];
+  int64_t n[N_KINDS];
+  const int rc = timing_collect(ms, n);
+  if (rc != CVM_OK) return rc;
+  if (ms_gram) *ms_gram = ms[KIND_FOLD];
+  if (n_gram) *n_gram = n[KIND_FOLD];
+  if (ms_acc) *ms_acc = ms[KIND_STREAM];
+  if (n_acc) *n_acc = n[KIND_STREAM];
+  return CVM_OK;
 }
 
 int cvm_clock_probe(void *device_buf, size_t bytes) {

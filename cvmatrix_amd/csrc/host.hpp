@@ -27,7 +27,8 @@ std::atomic<bool> g_timing{false};
 std::mutex g_timing_mu;
 TimedLaunch g_timed[MAX_TIMED];
 int g_ntimed = 0;        // slots handed out (guarded by g_timing_mu)
-// kinds: 0 Gram launch of the fit stage, 1 of the fold stage, 2 small_stats_kernel, 3 the small-fold update kernels
+// kinds: 0 Gram launch of the fit stage, 1 of the fold stage, 2 small_stats_kernel, 3 the small-fold update kernels,
+// 4 stream_accumulate_kernel (cvm_stream_add)
 inline TimedLaunch *timed_begin(int kind, hipStream_t st) {
   if (!g_timing.load(std::memory_order_relaxed)) return nullptr;
   TimedLaunch *tl = nullptr;
@@ -44,7 +45,7 @@ inline TimedLaunch *timed_begin(int kind, hipStream_t st) {
   return tl;
 }
 inline void timed_end(TimedLaunch *tl, hipStream_t st) { if (tl) (void)hipEventRecord(tl->b, st); }
-enum { KIND_FIT = 0, KIND_FOLD = 1 };
+enum { KIND_FIT = 0, KIND_FOLD = 1, KIND_STREAM = 4, N_KINDS = 5 };
 
 // ---- optional clock probe of the product Gram kernel (cvm_clock_probe) -------------------
 // A caller-owned device buffer; while one is set every LDS-DMA Gram launch of the process hands it to the

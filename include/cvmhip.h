@@ -217,6 +217,55 @@ int cvm_sweep_unions(const int64_t *fold_offsets, int64_t n_total,
                      double *out_fold, const void *sweep_ws, size_t sweep_ws_bytes, int64_t splits,
                      void *ws, size_t ws_bytes, void *stream);
 
+/* Streaming cross-validation: the folds' raw updates accumulated over ROW CHUNKS, for data that is larger
+ * than device memory or arrives in batches (no reference counterpart: cvmatrix.py's fit takes all rows at
+ * once, :207-328).  Every quantity the fold stage reads -- U_f = X_f^T W X_f | X_f^T W Y_f, the column
+ * sums, sw_f, nz_f -- is a sum over rows, hence over chunks.
+ *   accumulator   device, cvm_stream_workspace_bytes(CVM_STREAM_ACCUMULATOR, ..) bytes, 16-byte aligned:
+ *                 one float64 unit per fold (both dtypes) and behind the units the statistics region
+ *                 cvm_sweep_fold_range carves
+ *   state         host int64[CVM_STREAM_STATE_LEN]: the stream's header (shape it was reset with, chunks
+ *                 and rows added); the caller keeps it next to the accumulator and does not edit it
+ * cvm_stream_reset  zeroes the accumulator and fills the header.
+ * cvm_stream_add    one chunk: X, Y (NULL iff M == 0), w (NULL: unweighted; the same for every chunk of a
+ *                 stream) hold n_rows rows; idx / offsets (device) / host_offsets group the chunk's rows by
+ *                 fold as in cvm_sweep_fit -- chunk-local row numbers, fold position = label, empty folds
+ *                 allowed.  Launches the Gram kernel exactly as cvm_sweep_fit does, into `ws`
+ *                 (cvm_stream_workspace_bytes(CVM_STREAM_SCRATCH, n_folds, the chunk's longest fold, ..);
+ *                 contents before and after do not matter), and one kernel that adds every fold's chunk
+ *                 update -- the ordered float64 sum of its row-split slots -- to the accumulator.  A fold
+ *                 without rows in the chunk is skipped; n_rows == 0 launches nothing.  info (host, NULL or
+ *                 int64[2]): the chunk's plan token (s_off | s_diag << 20) and the bytes the accumulate
+ *                 kernel moves.
+ * cvm_stream_close  makes the accumulated state readable: G, H, gstats = the fold-ordered sum of the units
+ *                 (as cvm_sweep_fit forms them), neg_flag as there; *units_out / *units_bytes_out /
+ *                 *splits_out are the workspace, its size and the plan token (one slot per fold) that
+ *                 cvm_sweep_fold_range and cvm_sweep_unions accept as they are.  float64: the workspace is
+ *                 the accumulator itself (ws may be NULL).  float32: every accumulated element is rounded
+ *                 once into `ws` (cvm_stream_workspace_bytes(CVM_STREAM_CLOSE, ..)).  The units of the
+ *                 accumulator are not written: more chunks may follow, and a later close sees them all.
+ *                 Those two entry points read `offsets` only for the row counts of unweighted folds: pass
+ *                 the cumulative totals of the accumulated fold sizes.
+ * The bits depend on the chunks and their order alone; a stream of ONE chunk gives the bits of
+ * cvm_sweep_fit + cvm_sweep_folds over the same folds.  No atomics.  CVM_EINVAL (negative sizes, decreasing
+ * offsets, offsets that do not add up to n_rows, n_folds / K / M / dtype other than the header's, weights in
+ * some chunks only) and CVM_EWORKSPACE (accumulator or workspace too small) are decided before the device is
+ * touched. */
+#define CVM_STREAM_ACCUMULATOR 0
+#define CVM_STREAM_SCRATCH 1
+#define CVM_STREAM_CLOSE 2
+#define CVM_STREAM_STATE_LEN 8
+size_t cvm_stream_workspace_bytes(int what, int64_t n_folds, int64_t max_fold_rows, int K, int M, int dtype);
+int cvm_stream_reset(void *acc, size_t acc_bytes, int64_t n_folds, int K, int M, int dtype, int64_t *state,
+                     void *stream);
+int cvm_stream_add(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
+                   const int64_t *host_offsets, int64_t n_folds, int64_t n_rows, int K, int M, int dtype,
+                   void *acc, size_t acc_bytes, int64_t *state, void *ws, size_t ws_bytes, void *stream,
+                   int64_t *info);
+int cvm_stream_close(void *acc, size_t acc_bytes, const int64_t *state, int64_t n_folds, int K, int M, int dtype,
+                     void *G, void *H, double *gstats, int32_t *neg_flag, void *ws, size_t ws_bytes, void *stream,
+                     void **units_out, size_t *units_bytes_out, int64_t *splits_out);
+
 /* Device-side Partitioner (replaces cvmatrix/partitioner.py:89-107 for integer labels):
  *   labels      int64[N], one fold label per row, each in [0, n_labels) (up to 4096 labels: one
  *               stable counting sort; more, e.g. leave-one-out with a label per row: the same
@@ -483,6 +532,8 @@ int cvm_timing_read(double *ms_fit, int64_t *n_fit, double *ms_fold, int64_t *n_
  * statistics kernel of the small-fold route (small_stats_kernel), [3] its update kernels (everything
  * a call launches after the statistics: tile / whole-rows kernel and the XTY panels). */
 int cvm_timing_read_kinds(double *ms4, int64_t *n4);
+/* The same for a stream: the Gram launches (kind 1) and the accumulate kernels of cvm_stream_add. */
+int cvm_timing_read_stream(double *ms_gram, int64_t *n_gram, double *ms_acc, int64_t *n_acc);
 
 /* Benchmark support: the write ceiling of this device, measured with the product's own kind of store --
  * one launch that fills `bytes` (a multiple of 16) from `buf` (16-byte aligned) with zeros by nontemporal
