@@ -34,7 +34,7 @@ EXPORTS = (
     "cvm_pls_workspace_bytes", "cvm_pls_fit", "cvm_pls_plan",
     "cvm_pls_sse_workspace_bytes", "cvm_pls_validation_sse",
     "cvm_ridge_workspace_bytes", "cvm_ridge_fit",
-    "cvm_pcr_workspace_bytes", "cvm_pcr_fit",
+    "cvm_pcr_workspace_bytes", "cvm_pcr_fit", "cvm_pcr_blocked_workspace_bytes", "cvm_pcr_blocked_fit",
     "cvm_enet_workspace_bytes", "cvm_enet_fit",
     "cvm_omp_workspace_bytes", "cvm_omp_fit",
     "cvm_cv_predict", "cvm_cv_predict_plan",
@@ -148,6 +148,11 @@ def load():
     lib.cvm_pcr_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
     lib.cvm_pcr_fit.restype = C.c_int
     lib.cvm_pcr_fit.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, dbl, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.cvm_pcr_blocked_workspace_bytes.restype = sz
+    lib.cvm_pcr_blocked_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.cvm_pcr_blocked_fit.restype = C.c_int
+    lib.cvm_pcr_blocked_fit.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, dbl, C.c_int, vp, vp, vp, vp,
+                                        vp, vp, sz, vp]
     lib.cvm_enet_workspace_bytes.restype = sz
     lib.cvm_enet_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
     lib.cvm_enet_fit.restype = C.c_int

@@ -48,6 +48,7 @@ namespace {
 #include "pls.hpp"
 #include "ridge.hpp"
 #include "pcr.hpp"
+#include "pcr_blocked.hpp"
 #include "enet.hpp"
 #include "omp.hpp"
 #include "tile_product.hpp"
@@ -565,6 +566,32 @@ int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
     return pcr_fit_impl<float>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
                                (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_pcr_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_pcr_blocked_workspace_bytes(int64_t n_folds, int K, int M, int A) {
+  if (n_folds < 0 || K <= 0 || K > PCRB_MAXK || M < 0 || M > PCR_MAXM || A <= 0 || A > K) return 0;
+  return pcr_blocked_workspace_bytes(n_folds, K, M);
+}
+
+int cvm_pcr_blocked_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
+                        double rank_tol, int max_sweeps, void *B, double *eigenvalues, void *V, int32_t *n_fit,
+                        int32_t *sweeps, void *ws, size_t ws_bytes, void *stream) {
+  if (!XTX || !eigenvalues || !n_fit || !sweeps || !ws) return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: null pointer%s");
+  if (n_folds < 0 || K <= 0 || K > PCRB_MAXK || M < 0 || M > PCR_MAXM || A <= 0 || A > K)
+    return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: bad shape (1 <= K <= 4096, 1 <= A <= K, 0 <= M <= 64)%s");
+  if (M > 0 ? (!XTY || !B) : (XTY || B))
+    return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: XTY and B go with M > 0, neither with M == 0 (PCA only)%s");
+  if (!(rank_tol < 1.0)) return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: rank_tol must be below 1 (<= 0: the default)%s");
+  if (max_sweeps < 1 || max_sweeps > PCR_MAXSWEEPS)
+    return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: max_sweeps must be 1 .. 60%s");
+  if (rank_tol <= 0.0) rank_tol = 32.0 * K * 0x1p-52;
+  if (dtype == CVM_F64)
+    return pcr_blocked_fit_impl<double>(XTX, XTY, n_folds, K, M, A, rank_tol, max_sweeps, B, eigenvalues, V, n_fit,
+                                        sweeps, ws, ws_bytes, (hipStream_t)stream);
+  if (dtype == CVM_F32)
+    return pcr_blocked_fit_impl<float>(XTX, XTY, n_folds, K, M, A, rank_tol, max_sweeps, B, eigenvalues, V, n_fit,
+                                       sweeps, ws, ws_bytes, (hipStream_t)stream);
+  return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: dtype must be CVM_F32 or CVM_F64%s");
 }
 
 // shapes of cvm_cv_predict / cvm_cv_predict_plan: an error message, or nullptr

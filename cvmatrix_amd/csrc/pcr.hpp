@@ -49,6 +49,102 @@ __host__ __device__ inline int pcr_ld(int K, int M) { return ((K > M ? K : M) + 
 // bytes of one fold's slot: S and V, K rows of ld float64 each (256-byte aligned)
 inline size_t pcr_slot_bytes(int K, int M) { return align_up((size_t)2 * K * pcr_ld(K, M) * 8, 256); }
 
+// Steps 3 and 4 for one fold whose S is diagonal to the threshold, by the NT threads of its workgroup: what
+// pcr_kernel and the finish of the blocked solver (pcr_blocked.hpp) both end with.  S and V have leading
+// dimension ld; lam (K), sgn (A), ord (K) and gs (PCR_GBATCH) are the caller's, in LDS or in its slot; the
+// running sum acc (K x M) may take the place of S.
+template <typename T, int NT, typename O>
+__device__ __forceinline__ void pcr_finish_fold(const double *S, const double *V, const int ld, const int K, const int M,
+                                                const int A, const double rank_tol, const int sweeps_run, const T *Y,
+                                                T *Bo, T *Vo, double *Eo, int32_t *n_fit_out, int32_t *sweeps_out,
+                                                double *lam, double *sgn, double *gs, O *ord, int *nfit_s, double *acc,
+                                                const int tid) {
+  // 3. eigenvalues in descending order (counting rank, ties by index)
+  for (int j = tid; j < K; j += NT) {
+    lam[j] = S[(size_t)j * ld + j];
+    ord[j] = (O)j;                                    // (every entry an index, whatever the comparisons below say)
+  }
+  __syncthreads();
+  for (int j = tid; j < K; j += NT) {
+    const double lj = lam[j];
+    int rank = 0;
+    for (int i = 0; i < K; ++i) rank += (lam[i] > lj) || (lam[i] == lj && i < j);
+    ord[rank] = (O)j;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double cut = rank_tol * lam[ord[0]];
+    int n = 0;
+    for (int j = 0; j < K; ++j) n += lam[j] > cut;
+    *nfit_s = n < A ? n : A;
+  }
+  // sign: the entry of largest magnitude positive, the lowest index among equals
+  for (int c = tid; c < A; c += NT) {
+    const int col = ord[c];
+    double best = -1.0, sg = 1.0;
+    for (int k = 0; k < K; ++k) {
+      const double v = V[(size_t)k * ld + col];
+      if (fabs(v) > best) { best = fabs(v); sg = v < 0.0 ? -1.0 : 1.0; }
+    }
+    sgn[c] = sg;
+  }
+  __syncthreads();
+  const int nfit = *nfit_s;
+  for (int c = tid; c < A; c += NT) Eo[c] = lam[ord[c]];
+  if (Vo)
+    for (int e = tid; e < K * A; e += NT) {
+      const int k = e / A, c = e - k * A;
+      Vo[e] = c < nfit ? (T)(sgn[c] * V[(size_t)k * ld + ord[c]]) : (T)0.0;
+    }
+  if (tid == 0) {
+    *n_fit_out = nfit;
+    *sweeps_out = sweeps_run;
+  }
+
+  // 4. coefficients: the running sum acc[k][m], components in batches whose (v_j^T XTY) / lambda_j fit gs
+  if (Bo) {
+    const int KM = K * M;
+    __syncthreads();                                  // (lam was read from S by other threads)
+    if (nfit == 0)
+      for (size_t i = tid; i < (size_t)A * KM; i += NT) Bo[i] = (T)0.0;
+    const int jb = PCR_GBATCH / M;                    // components per batch (>= 32)
+    for (int j0 = 0; j0 < nfit; j0 += jb) {
+      const int nj = nfit - j0 < jb ? nfit - j0 : jb;
+      for (int e = tid; e < nj * M; e += NT) {
+        const int j = e / M, mm = e - j * M;
+        const int col = ord[j0 + j];
+        // v^T XTY[:, mm] cancels (a random direction against K entries): the products exactly by fma and
+        // the roundings of the running sum carried along (a compensated dot product, k in order), so that
+        // its error is a rounding of the result and not K roundings of the largest partial sum
+        double g = 0.0, comp = 0.0;
+        for (int k = 0; k < K; ++k) {
+          const double x = V[(size_t)k * ld + col], y = (double)Y[(size_t)k * M + mm];
+          const double pr = x * y, pe = fma(x, y, -pr);
+          const double t = g + pr, z = t - g;
+          comp += ((g - (t - z)) + (pr - z)) + pe;
+          g = t;
+        }
+        gs[e] = (g + comp) / lam[col];
+      }
+      __syncthreads();
+      for (int e = tid; e < KM; e += NT) {
+        const int k = e / M, mm = e - k * M;
+        double s = j0 ? acc[e] : 0.0;
+        for (int j = 0; j < nj; ++j) {
+          s += V[(size_t)k * ld + ord[j0 + j]] * gs[j * M + mm];
+          Bo[(size_t)(j0 + j) * KM + e] = (T)s;
+        }
+        if (j0 + nj < nfit) {
+          acc[e] = s;
+        } else {
+          for (int c = nfit; c < A; ++c) Bo[(size_t)c * KM + e] = (T)s;   // more components than exist
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(PCR_THREADS) void pcr_kernel(const PcrArgs a) {
   __shared__ double red[PCR_THREADS];
@@ -228,92 +324,10 @@ __global__ __launch_bounds__(PCR_THREADS) void pcr_kernel(const PcrArgs a) {
       continue;
     }
 
-    // 3. eigenvalues in descending order (counting rank, ties by index)
-    for (int j = tid; j < K; j += PCR_THREADS) {
-      lam[j] = S[(size_t)j * ld + j];
-      ord[j] = (short)j;                              // (every entry an index, whatever the comparisons below say)
-    }
-    __syncthreads();
-    for (int j = tid; j < K; j += PCR_THREADS) {
-      const double lj = lam[j];
-      int rank = 0;
-      for (int i = 0; i < K; ++i) rank += (lam[i] > lj) || (lam[i] == lj && i < j);
-      ord[rank] = (short)j;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const double cut = a.rank_tol * lam[ord[0]];
-      int n = 0;
-      for (int j = 0; j < K; ++j) n += lam[j] > cut;
-      nfit_s = n < A ? n : A;
-    }
-    // sign: the entry of largest magnitude positive, the lowest index among equals
-    for (int c = tid; c < A; c += PCR_THREADS) {
-      const int col = ord[c];
-      double best = -1.0, sg = 1.0;
-      for (int k = 0; k < K; ++k) {
-        const double v = V[(size_t)k * ld + col];
-        if (fabs(v) > best) { best = fabs(v); sg = v < 0.0 ? -1.0 : 1.0; }
-      }
-      sgn[c] = sg;
-    }
-    __syncthreads();
-    const int nfit = nfit_s;
-    for (int c = tid; c < A; c += PCR_THREADS) Eo[c] = lam[ord[c]];
-    if (Vo)
-      for (int e = tid; e < K * A; e += PCR_THREADS) {
-        const int k = e / A, c = e - k * A;
-        Vo[e] = c < nfit ? (T)(sgn[c] * V[(size_t)k * ld + ord[c]]) : (T)0.0;
-      }
-    if (tid == 0) {
-      a.n_fit[f] = nfit;
-      a.sweeps[f] = status;
-    }
-
-    // 4. coefficients: the running sum acc[k][m] takes the place of S (K * M <= K * ld), components in
-    //    batches whose (v_j^T XTY) / lambda_j fit gs
-    if (Bo) {
-      double *acc = S;
-      const int KM = K * M;
-      __syncthreads();                                // (lam was read from S by other threads)
-      if (nfit == 0)
-        for (size_t i = tid; i < (size_t)A * KM; i += PCR_THREADS) Bo[i] = (T)0.0;
-      const int jb = PCR_GBATCH / M;                  // components per batch (>= 32)
-      for (int j0 = 0; j0 < nfit; j0 += jb) {
-        const int nj = nfit - j0 < jb ? nfit - j0 : jb;
-        for (int e = tid; e < nj * M; e += PCR_THREADS) {
-          const int j = e / M, mm = e - j * M;
-          const int col = ord[j0 + j];
-          // v^T XTY[:, mm] cancels (a random direction against K entries): the products exactly by fma and
-          // the roundings of the running sum carried along (a compensated dot product, k in order), so that
-          // its error is a rounding of the result and not K roundings of the largest partial sum
-          double g = 0.0, comp = 0.0;
-          for (int k = 0; k < K; ++k) {
-            const double x = V[(size_t)k * ld + col], y = (double)Y[(size_t)k * M + mm];
-            const double pr = x * y, pe = fma(x, y, -pr);
-            const double t = g + pr, z = t - g;
-            comp += ((g - (t - z)) + (pr - z)) + pe;
-            g = t;
-          }
-          gs[e] = (g + comp) / lam[col];
-        }
-        __syncthreads();
-        for (int e = tid; e < KM; e += PCR_THREADS) {
-          const int k = e / M, mm = e - k * M;
-          double s = j0 ? acc[e] : 0.0;
-          for (int j = 0; j < nj; ++j) {
-            s += V[(size_t)k * ld + ord[j0 + j]] * gs[j * M + mm];
-            Bo[(size_t)(j0 + j) * KM + e] = (T)s;
-          }
-          if (j0 + nj < nfit) {
-            acc[e] = s;
-          } else {
-            for (int c = nfit; c < A; ++c) Bo[(size_t)c * KM + e] = (T)s;   // more components than exist
-          }
-        }
-        __syncthreads();
-      }
-    }
+    // 3. and 4. the ordering, the signs, n_fit and the coefficients; the running sum takes the place of S
+    //    (K * M <= K * ld)
+    pcr_finish_fold<T, PCR_THREADS>(S, V, ld, K, M, A, a.rank_tol, status, Y, Bo, Vo, Eo, a.n_fit + f, a.sweeps + f, lam,
+                                    sgn, gs, ord, &nfit_s, S, tid);
     __syncthreads();
   }
 }

@@ -402,6 +402,37 @@ size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A);
 int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
                 double rank_tol, void *B, double *eigenvalues, void *V, int32_t *n_fit, int32_t *sweeps,
                 void *ws, size_t ws_bytes, void *stream);
+/* The same PCA / PCR with a second eigensolver, for 1 <= K <= 4096: a cyclic two-sided BLOCK Jacobi method
+ * (blocks of 32 indices, the round-robin order above applied to blocks), many workgroups per fold.  A round is
+ * two launches: one workgroup per pair of blocks runs one scalar Jacobi sweep (the rotation formulas and the
+ * rule of cvm_pcr_fit: pair (p,q) rotates iff |S_pq| > 2^-52 ||XTX[f]||_F) on the pair's 64 x 64 diagonal tile
+ * and keeps the product Q of its rotations; then one workgroup per off-diagonal tile of S and per tile of V
+ * applies Q^T . Q and . Q by 64 x 64 x 64 float64 matrix-core products, writing the mirror tile of S as the
+ * transpose of the same numbers.  No workgroup waits for another; the launches are ordered by the stream.
+ *   XTX, XTY, rank_tol, B, eigenvalues, V, n_fit: as cvm_pcr_fit, word for word (eigenvalues descending by
+ *        counting rank, ties by index; in every component the entry of largest magnitude positive; n_fit =
+ *        min(A, number of lambda_j > rank_tol * lambda_0), default rank_tol 32 K 2^-52; B[f][a] for a >= n_fit
+ *        has the bits of B[f][n_fit - 1]; components a >= n_fit are exactly zero), with 1 <= K <= 4096
+ *   max_sweeps  1 .. 60: a fold that has not converged after that many sweeps is NaN throughout, sweeps -1
+ *   sweeps int32[n_folds]: block sweeps run (the last one made no rotation), 1 .. max_sweeps; 0 with n_fit -1
+ *        for a fold with a NaN or an infinity in its XTX or XTY (NaN throughout, no rotation run)
+ *   ws   cvm_pcr_blocked_workspace_bytes(n_folds, K, M, A) for min(n_folds, 512) folds in flight (host
+ *        arithmetic, no device query).  A slot holds S and V padded to Kp = 32 * (ceil(K / 32) rounded up to
+ *        even), Kp / 64 matrices Q, the flag words and the running sum of the coefficients, 256-byte aligned
+ *        (about 270 MB at K = 4096).  Any workspace that holds one slot gives the same bits; less:
+ *        CVM_EWORKSPACE.  Bad pointers, shapes, rank_tol, max_sweeps or dtype: CVM_EINVAL
+ *        (cvm_pcr_blocked_workspace_bytes: 0).  n_folds == 0: nothing is launched.
+ * THIS ENTRY WAITS FOR THE DEVICE ONCE PER SWEEP, unlike cvm_pcr_fit: after every sweep it copies one status
+ * word per fold of the batch on `stream` and waits for the copy; converged folds are finished and drop out,
+ * the rest get another sweep.  It therefore cannot be captured into a graph: on a capturing stream it returns
+ * CVM_EINVAL without launching or synchronising anything.
+ * Arithmetic in float64 for both dtypes, no float atomics, every sum in a fixed order; a fold's bits depend on
+ * its own matrices, rank_tol and max_sweeps alone, not on its place in the batch, the batch size, the
+ * workspace size, which other folds have finished or what the workspace held. */
+size_t cvm_pcr_blocked_workspace_bytes(int64_t n_folds, int K, int M, int A);
+int cvm_pcr_blocked_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
+                        double rank_tol, int max_sweeps, void *B, double *eigenvalues, void *V,
+                        int32_t *n_fit, int32_t *sweeps, void *ws, size_t ws_bytes, void *stream);
 /* Elastic net and lasso over a grid of penalties for every fold (the sparse member of the family; no
  * counterpart in the reference): for fold f, response m and penalty l, with G = XTX[f], h = XTY[f][:, m],
  *   B[f][l][:, m] = argmin over beta of
