@@ -47,6 +47,7 @@ namespace {
 #include "partition.hpp"
 #include "pls.hpp"
 #include "ridge.hpp"
+#include "lda.hpp"
 #include "pcr.hpp"
 #include "pcr_blocked.hpp"
 #include "enet.hpp"
@@ -489,6 +490,32 @@ int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int 
   if (dtype == CVM_F32)
     return ridge_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_ridge_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_lda_workspace_bytes(int64_t n_folds, int K, int C, int L) {
+  if (n_folds < 0 || K <= 0 || K > RIDGE_MAXK || C < 2 || C > LDA_MAXC || L <= 0 || L > RIDGE_MAXL) return 0;
+  return lda_workspace_bytes(n_folds, K, C, L);
+}
+
+int cvm_lda_fit(const void *XTX, const void *XTY, const double *class_w, int64_t n_folds, int K, int C,
+                const double *shrinkage, int L, int dtype, void *coef, void *intercept, int32_t *info, void *ws,
+                size_t ws_bytes, void *stream) {
+  // (everything below is decided before the device is touched)
+  if (!XTX || !XTY || !class_w || !shrinkage || !coef || !intercept || !info || !ws)
+    return fail(CVM_EINVAL, "cvm_lda_fit: null pointer%s");
+  if (n_folds < 0 || K <= 0 || K > RIDGE_MAXK || C < 2 || C > LDA_MAXC)
+    return fail(CVM_EINVAL, "cvm_lda_fit: bad shape (1 <= K <= 4096, 2 <= C <= 64)%s");
+  if (L <= 0 || L > RIDGE_MAXL) return fail(CVM_EINVAL, "cvm_lda_fit: 1 <= L <= 256 shrinkage values%s");
+  for (int l = 0; l < L; ++l)
+    if (!(shrinkage[l] >= 0.0 && shrinkage[l] <= 1.0))
+      return fail(CVM_EINVAL, "cvm_lda_fit: every shrinkage must lie in [0, 1]%s");
+  if (dtype == CVM_F64)
+    return lda_fit_impl<double>(XTX, XTY, class_w, n_folds, K, C, shrinkage, L, coef, intercept, info, ws, ws_bytes,
+                                (hipStream_t)stream);
+  if (dtype == CVM_F32)
+    return lda_fit_impl<float>(XTX, XTY, class_w, n_folds, K, C, shrinkage, L, coef, intercept, info, ws, ws_bytes,
+                               (hipStream_t)stream);
+  return fail(CVM_EINVAL, "cvm_lda_fit: dtype must be CVM_F32 or CVM_F64%s");
 }
 
 size_t cvm_enet_workspace_bytes(int64_t n_folds, int K, int M, int L) {

@@ -366,6 +366,45 @@ int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const in
 size_t cvm_ridge_workspace_bytes(int64_t n_folds, int K, int M, int L);
 int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, const double *lambdas, int L,
                   int dtype, void *B, int32_t *info, void *ws, size_t ws_bytes, void *stream);
+/* Linear discriminant analysis with shrinkage for every fold (the classifier of the family; no counterpart in
+ * the reference), from the training matrices alone.  With h_c = XTY[f][:, c], n_c = class_w[f][c], n = sum_c n_c
+ * and m_c = h_c / n_c:
+ *   S_w = XTX[f] - sum_c h_c h_c' / n_c,   Sigma_g = (1 - g) S_w / n + g (tr S_w / (n K)) I
+ *   coef[f][l][:, c] = Sigma_g^-1 m_c,     intercept[f][l][c] = -1/2 m_c' coef[f][l][:, c] + log(n_c / n)
+ * for g = shrinkage[l]: scikit-learn's LinearDiscriminantAnalysis(solver="lsqr", shrinkage=g) up to a term common
+ * to all classes, PROVIDED that X is centred on the training set (CVM_CENTER_X) and Y is the unscaled 0/1 class
+ * indicator with one 1 per row, which the call cannot see.  The discriminant of a row z standardised by the
+ * fold's statistics is z' coef + intercept (cvm_cv_predict with muY = sdY = NULL, plus the intercept).
+ * Three stages: S' = (K / tr S_w) S_w and the m_c into the workspace (lda_moments_kernel, lda_scatter_kernel);
+ * (S' + g / (1 - g) I) x = m_c by the solver of cvm_ridge_fit for every g < 1; scaling and intercepts
+ * (lda_finish_kernel; g = 1 takes x = m_c with no solve).
+ *   XTX, XTY   [n_folds][K][K] and [n_folds][K][C] in `dtype`, 1 <= K <= 4096, 2 <= C <= 64 (not modified; the
+ *              upper triangle of XTX is the one used, both are checked for values that are not finite)
+ *   class_w    float64[n_folds][C]: the training weight of every class (its row count when unweighted)
+ *   shrinkage  HOST float64[L], 1 <= L <= 256, each in [0, 1] (copied into the launches)
+ *   coef       [n_folds][L][K][C] in `dtype`: the layout cvm_cv_predict takes, g in place of components
+ *   intercept  [n_folds][L][C] in `dtype`
+ *   info       int32[n_folds][L]: 0; j > 0 where the j-th pivot of the factorisation was not positive (a
+ *              singular S_w at g = 0); -1 where the fold holds a value of XTX, XTY or class_w that is not finite,
+ *              a negative class_w, or n or tr S_w that is not > 0.  Where info != 0 every coef and intercept
+ *              of that (fold, g) is NaN (never half-written); the fold's other g keep the bits they have
+ *              without the failure.  A class with n_c == 0 is absent from the fold: coef 0, intercept -inf
+ *   ws         cvm_lda_workspace_bytes(n_folds, K, C, L): the fold records (S', m, x: (K + C + L C) K float64
+ *              a fold and a few words) plus cvm_ridge_workspace_bytes(n_folds, K, C, L).  The smallest that
+ *              runs is one fold record and one factorisation,
+ *                cvm_lda_workspace_bytes(1, K, C, L) - cvm_ridge_workspace_bytes(1, K, C, L)
+ *                                                    + cvm_ridge_workspace_bytes(1, K, C, 1);
+ *              anything between runs fewer folds or factorisations at a time with the same results to the
+ *              bit.  Less: CVM_EWORKSPACE.  Bad pointers, shapes, shrinkage (NaN included) or dtype: CVM_EINVAL,
+ *              decided before the device is touched (cvm_lda_workspace_bytes: 0).  n_folds == 0: nothing is
+ *              launched.
+ * Arithmetic in float64 for both dtypes (float32 inputs widened on load, outputs rounded once on store), no
+ * float atomics, every sum in a fixed order, S' symmetric to the bit: a fold's bits depend on its own XTX, XTY,
+ * class_w and the grid alone, not on the batch around it or on the workspace size. */
+size_t cvm_lda_workspace_bytes(int64_t n_folds, int K, int C, int L);
+int cvm_lda_fit(const void *XTX, const void *XTY, const double *class_w /* [F][C] */, int64_t n_folds, int K, int C,
+                const double *shrinkage, int L, int dtype, void *coef /* [F][L][K][C] */, void *intercept /* [F][L][C] */,
+                int32_t *info /* [F][L] */, void *ws, size_t ws_bytes, void *stream);
 /* PCA and principal component regression for every fold (the two consumers of the training matrices that
  * the reference's CVMatrix docstring names next to PLS and OLS): the A leading eigenpairs of XTX[f],
  *   XTX[f] v_j = lambda_j v_j,  lambda_0 >= lambda_1 >= ...,
