@@ -35,6 +35,7 @@ EXPORTS = (
     "cvm_pls_sse_workspace_bytes", "cvm_pls_validation_sse",
     "cvm_ridge_workspace_bytes", "cvm_ridge_fit",
     "cvm_lda_workspace_bytes", "cvm_lda_fit",
+    "cvm_pcalda_workspace_bytes", "cvm_pcalda_fit",
     "cvm_pcr_workspace_bytes", "cvm_pcr_fit", "cvm_pcr_blocked_workspace_bytes", "cvm_pcr_blocked_fit",
     "cvm_enet_workspace_bytes", "cvm_enet_fit",
     "cvm_omp_workspace_bytes", "cvm_omp_fit",
@@ -149,6 +150,11 @@ def load():
     lib.cvm_lda_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
     lib.cvm_lda_fit.restype = C.c_int
     lib.cvm_lda_fit.argtypes = [vp, vp, vp, i64, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp]
+    lib.cvm_pcalda_workspace_bytes.restype = sz
+    lib.cvm_pcalda_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.cvm_pcalda_fit.restype = C.c_int
+    lib.cvm_pcalda_fit.argtypes = [vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, C.c_int, dbl, vp, vp, vp, vp,
+                                   vp, sz, vp]
     lib.cvm_pcr_workspace_bytes.restype = sz
     lib.cvm_pcr_workspace_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
     lib.cvm_pcr_fit.restype = C.c_int

@@ -52,6 +52,7 @@ namespace {
 #include "pcr_blocked.hpp"
 #include "enet.hpp"
 #include "omp.hpp"
+#include "pcalda.hpp"
 #include "tile_product.hpp"
 #include "validation_sse.hpp"
 #include "predict.hpp"
@@ -569,6 +570,32 @@ int cvm_omp_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
     return omp_fit_impl<float>(XTX, XTY, n_folds, K, M, A, normalize, rank_tol, B, support, n_fit, ws, ws_bytes,
                                (hipStream_t)stream);
   return fail(CVM_EINVAL, "cvm_omp_fit: dtype must be CVM_F32 or CVM_F64%s");
+}
+
+size_t cvm_pcalda_workspace_bytes(int64_t n_folds, int K, int C, int A) {
+  if (n_folds < 0 || K <= 0 || K > PCL_MAXK || C < 2 || C > PCL_MAXC || A <= 0 || A > K || A > PCL_CAP) return 0;
+  return pcalda_workspace_bytes(n_folds, K, C, A);
+}
+
+int cvm_pcalda_fit(const void *V, const double *eigenvalues, const int32_t *n_comp, const void *XTY,
+                   const double *class_w, int64_t n_folds, int K, int C, int A, int dtype, double pivot_tol,
+                   void *coef, void *intercept, int32_t *n_fit, int32_t *info, void *ws, size_t ws_bytes,
+                   void *stream) {
+  // (everything below is decided before the device is touched)
+  if (n_folds < 0 || K <= 0 || K > PCL_MAXK || C < 2 || C > PCL_MAXC)
+    return fail(CVM_EINVAL, "cvm_pcalda_fit: bad shape (1 <= K <= 4096, 2 <= C <= 64)%s");
+  if (A <= 0 || A > K || A > PCL_CAP) return fail(CVM_EINVAL, "cvm_pcalda_fit: 1 <= A <= min(K, 64) components%s");
+  if (!(pivot_tol < 1.0)) return fail(CVM_EINVAL, "cvm_pcalda_fit: pivot_tol must be below 1 (<= 0: the default)%s");
+  if (dtype != CVM_F64 && dtype != CVM_F32) return fail(CVM_EINVAL, "cvm_pcalda_fit: dtype must be CVM_F32 or CVM_F64%s");
+  if (n_folds == 0) return CVM_OK;
+  if (!V || !eigenvalues || !n_comp || !XTY || !class_w || !coef || !intercept || !n_fit || !info || !ws)
+    return fail(CVM_EINVAL, "cvm_pcalda_fit: null pointer%s");
+  if (pivot_tol <= 0.0) pivot_tol = PCL_PIVOT_TOL;
+  if (dtype == CVM_F64)
+    return pcalda_fit_impl<double>(V, eigenvalues, n_comp, XTY, class_w, n_folds, K, C, A, pivot_tol, coef, intercept,
+                                   n_fit, info, ws, ws_bytes, (hipStream_t)stream);
+  return pcalda_fit_impl<float>(V, eigenvalues, n_comp, XTY, class_w, n_folds, K, C, A, pivot_tol, coef, intercept,
+                                n_fit, info, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A) {

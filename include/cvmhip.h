@@ -405,6 +405,55 @@ size_t cvm_lda_workspace_bytes(int64_t n_folds, int K, int C, int L);
 int cvm_lda_fit(const void *XTX, const void *XTY, const double *class_w /* [F][C] */, int64_t n_folds, int K, int C,
                 const double *shrinkage, int L, int dtype, void *coef /* [F][L][K][C] */, void *intercept /* [F][L][C] */,
                 int32_t *info /* [F][L] */, void *ws, size_t ws_bytes, void *stream);
+/* PCA-LDA for every fold (the count-tuned classifier of the family; no counterpart in the reference): linear
+ * discriminant analysis on the scores of the first 1, 2, .., A principal components, from the eigenpairs that
+ * cvm_pcr_fit or cvm_pcr_blocked_fit return, the class sums and the class weights.  With h_c = XTY[f][:, c],
+ * n_c = class_w[f][c], n = sum_c n_c, V = V[f] (K x A) and lambda = eigenvalues[f]:
+ *   P = V' H,  m~_c = p_c / n_c (0 for an absent class),  S = diag(lambda) - sum_c p_c p_c' / n_c
+ *   S = L L' column by column; the path ends before component j (counted from 0) when j >= n_comp[f] or the pivot
+ *       d_j^2 = S_jj - sum_{i<j} L_ji^2 is not > pivot_tol lambda_j: n_fit[f] = j
+ *   Z = L^-1 M~,  W = V L^-T
+ *   coef[f][a] = coef[f][a-1] + w_a (n z_a)',   intercept[f][a] = intercept[f][a-1] - 1/2 (n z_a) o z_a,
+ *   coef[f][-1] = 0,  intercept[f][-1][c] = log(n_c / n)
+ * coef[f][a], intercept[f][a] are the discriminants on a+1 components, scikit-learn's Pipeline(PCA(a+1),
+ * LinearDiscriminantAnalysis(solver="lsqr")) up to a term common to all classes, PROVIDED that X is centred on the
+ * training set (CVM_CENTER_X) and Y is the unscaled 0/1 class indicator, which the call cannot see.  The
+ * discriminant of a row z standardised by the fold's statistics is z' coef + intercept (cvm_cv_predict with
+ * muY = sdY = NULL, plus the intercept).
+ *   V          [n_folds][K][A] in `dtype`, eigenvalues float64[n_folds][A] descending, n_comp int32[n_folds]: the
+ *              V, eigenvalues and n_fit of cvm_pcr_fit; 1 <= K <= 4096, 1 <= A <= min(K, 64): the factor lies in
+ *              LDS with one row per lane.  n_comp above A counts as A
+ *   XTY        [n_folds][K][C] in `dtype`, 2 <= C <= 64;  class_w float64[n_folds][C]
+ *   pivot_tol  below 1; <= 0: the default 2^-26.  d_j^2 / lambda_j is the within-class share of component j's
+ *              variance: below the square root of the unit roundoff the classes are separated along it as well as
+ *              the arithmetic can tell
+ *   coef       [n_folds][A][K][C] in `dtype`: the layout cvm_cv_predict takes;  intercept [n_folds][A][C] in `dtype`.
+ *              For a >= n_fit[f] both have the bits of a = n_fit[f] - 1 (n_fit 0: coef 0, intercept the log priors).
+ *              A class with n_c == 0 is absent from the fold: coef 0, intercept -inf
+ *   n_fit      int32[n_folds]: the models that exist, 0 .. A; -1 for a flagged fold
+ *   info       int32[n_folds]: 0 all A models exist; 1 the path ended at n_comp[f] < A; 2 it ended at a pivot; -1
+ *              the fold is flagged: n_comp[f] < 0, a value of V or eigenvalues in a component < n_comp[f], of XTY or
+ *              of class_w that is not finite (or a pivot, by overflow), a negative class_w, or n not > 0.  Every
+ *              coef and intercept of a flagged fold is NaN (written in the same pass as the others: never
+ *              half-written); other folds keep their bits
+ *   ws         cvm_pcalda_workspace_bytes(n_folds, K, C, A): a record per fold (the shares of P of the
+ *              ceil(K / 128) row slices, L^-1, n Z: (ceil(K / 128) C + A + C) A float64 and a few words).  The
+ *              smallest that runs is cvm_pcalda_workspace_bytes(1, K, C, A); anything between takes as many folds
+ *              at a time as fit, with the same results to the bit.  Less: CVM_EWORKSPACE.  Shapes outside the
+ *              limits, a pivot_tol that is NaN or >= 1, a dtype that is none, or a null pointer with
+ *              n_folds > 0: CVM_EINVAL, decided before the device is touched (cvm_pcalda_workspace_bytes: 0).
+ *              n_folds == 0: nothing is launched.
+ * Three launches per chunk of folds: P by row slices of K (pcalda_project_kernel; the slices are added in
+ * ascending order, no float atomics), the factorisation, Z, L^-1 and the intercepts by one workgroup per fold
+ * (pcalda_factor_kernel), coef by one workgroup per (fold, tile of rows) (pcalda_expand_kernel).  Arithmetic in
+ * float64 for both dtypes (float32 inputs widened on load, outputs rounded once on store), every sum in a fixed
+ * order: a fold's bits depend on its own V, eigenvalues, n_comp, XTY, class_w, A and pivot_tol alone, not on the
+ * batch around it, the workspace size or the chunking. */
+size_t cvm_pcalda_workspace_bytes(int64_t n_folds, int K, int C, int A);
+int cvm_pcalda_fit(const void *V /* [F][K][A] */, const double *eigenvalues /* [F][A] */, const int32_t *n_comp /* [F] */,
+                   const void *XTY /* [F][K][C] */, const double *class_w /* [F][C] */, int64_t n_folds, int K, int C,
+                   int A, int dtype, double pivot_tol, void *coef /* [F][A][K][C] */, void *intercept /* [F][A][C] */,
+                   int32_t *n_fit /* [F] */, int32_t *info /* [F] */, void *ws, size_t ws_bytes, void *stream);
 /* PCA and principal component regression for every fold (the two consumers of the training matrices that
  * the reference's CVMatrix docstring names next to PLS and OLS): the A leading eigenpairs of XTX[f],
  *   XTX[f] v_j = lambda_j v_j,  lambda_0 >= lambda_1 >= ...,
