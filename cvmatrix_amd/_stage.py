@@ -4,8 +4,10 @@ argument rules + its output allocations + one ``launch`` (+ its ``check=True`` r
 
 from __future__ import annotations
 
+import math
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -41,6 +43,52 @@ def training_pair(who: str, XTX, XTY, *, y_optional: bool = False):
         raise ValueError("XTX and XTY must both be float64 or both float32.")
     F, K = XTX.shape[:2]
     return XTX.contiguous(), XTY, F, K, (0 if no_y else XTY.shape[2])
+
+
+def check_fit_dims(who_text: str, K: int, M: int, max_k: int, max_m: int) -> None:
+    """1 <= K <= max_k variables, 1 <= M <= max_m responses; ``who_text`` opens the message ("The device ridge")."""
+    if not 1 <= K <= max_k:
+        raise ValueError(f"{who_text} takes 1 <= K <= {max_k}.")
+    if not 1 <= M <= max_m:
+        raise ValueError(f"{who_text} takes 1 to {max_m} responses.")
+
+
+def check_tolerance(name: str, value) -> float:
+    """None or a value <= 0: 0.0 (the library's default); otherwise a float below 1."""
+    if value is None:
+        return 0.0
+    tol = float(value)
+    if math.isnan(tol) or tol >= 1.0:
+        raise ValueError(f"{name} must be below 1, got {value!r}.")
+    return max(tol, 0.0)
+
+
+def check_grid(name: str, values, limit: int, *, low_open: bool, high=None, scalar_ok: bool = False) -> np.ndarray:
+    """A grid of penalties as a contiguous 1-D float64 array: 1 to ``limit`` values (``scalar_ok``: or a scalar),
+    each finite and > 0 (``low_open``) or >= 0; with ``high``, each in [0, high] instead."""
+    v = np.asarray(values, dtype=np.float64)
+    if scalar_ok and v.ndim == 0:
+        v = v.reshape(1)
+    if v.ndim != 1:
+        raise ValueError(f"{name} must be {'a scalar or ' if scalar_ok else ''}one-dimensional, got shape {v.shape}.")
+    if not 1 <= v.size <= limit:
+        raise ValueError(f"{name} must hold 1 to {limit} values, got {v.size}.")
+    one = name.rstrip("s")                        # "every lambda" of "lambdas"
+    low_ok = v > 0 if low_open else v >= 0        # (NaN fails every comparison)
+    if high is not None:
+        if not np.all(low_ok & (v <= high)):
+            raise ValueError(f"every {one} must lie in {'(' if low_open else '['}0, {high}].")
+    elif not np.all(np.isfinite(v) & low_ok):
+        raise ValueError(f"every {one} must be finite and {'>' if low_open else '>='} 0.")
+    return np.ascontiguousarray(v)
+
+
+def check_count(name: str, value, top: int, what: str) -> int:
+    """``value`` as an int: an integer (no bool) with 1 <= value <= top; ``what`` is how the message writes the
+    upper bound ("K = 7")."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= value <= top:
+        raise ValueError(f"{name} must be an integer with 1 <= {name} <= {what}, got {value!r}.")
+    return int(value)
 
 
 def launch(what: str, dev, call, ws_bytes: int = 0, *, one: int = 0, limit: Optional[int] = None) -> None:

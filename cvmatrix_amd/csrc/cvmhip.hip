@@ -45,6 +45,7 @@ namespace {
 #include "fold_unions.hpp"
 #include "stream_accumulate.hpp"
 #include "partition.hpp"
+#include "fit_plan.hpp"
 #include "pls.hpp"
 #include "ridge.hpp"
 #include "lda.hpp"
@@ -444,11 +445,10 @@ int cvm_pls_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
   if (n_folds < 0 || K <= 0 || M <= 0 || A <= 0) return fail(CVM_EINVAL, "cvm_pls_fit: bad shape%s");
   if (M > PLS_MAXM) return fail(CVM_EINVAL, "cvm_pls_fit: at most 64 responses%s");
   if (A > PLS_MAXA) return fail(CVM_EINVAL, "cvm_pls_fit: at most 512 components%s");
-  if (dtype == CVM_F64)
-    return pls_fit_impl<double>(XTX, XTY, n_folds, K, M, A, B, W, P, Q, R, n_fit, status, ws, ws_bytes, (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return pls_fit_impl<float>(XTX, XTY, n_folds, K, M, A, B, W, P, Q, R, n_fit, status, ws, ws_bytes, (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_pls_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_pls_fit", [&](auto t) {
+    return pls_fit_impl<decltype(t)>(XTX, XTY, n_folds, K, M, A, B, W, P, Q, R, n_fit, status, ws, ws_bytes,
+                                     (hipStream_t)stream);
+  });
 }
 
 size_t cvm_pls_sse_workspace_bytes(int64_t n_folds, int64_t max_fold_rows, int M, int A) {
@@ -463,13 +463,10 @@ int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const in
   if (!X || !Y || !offsets || !B || !sse || !wsum || !ws) return fail(CVM_EINVAL, "cvm_pls_validation_sse: null pointer%s");
   if (n_folds < 0 || max_fold_rows < 0 || K <= 0 || M <= 0 || A <= 0 || (!idx && max_fold_rows > 0))
     return fail(CVM_EINVAL, "cvm_pls_validation_sse: bad shape%s");
-  if (dtype == CVM_F64)
-    return pls_sse_impl<double>(X, Y, w, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, sse, wsum, ws,
-                                ws_bytes, (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return pls_sse_impl<float>(X, Y, w, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, sse, wsum, ws,
-                               ws_bytes, (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_pls_validation_sse: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_pls_validation_sse", [&](auto t) {
+    return pls_sse_impl<decltype(t)>(X, Y, w, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, sse,
+                                     wsum, ws, ws_bytes, (hipStream_t)stream);
+  });
 }
 
 size_t cvm_ridge_workspace_bytes(int64_t n_folds, int K, int M, int L) {
@@ -486,11 +483,9 @@ int cvm_ridge_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int 
   for (int l = 0; l < L; ++l)
     if (!(lambdas[l] >= 0.0) || lambdas[l] == HUGE_VAL)
       return fail(CVM_EINVAL, "cvm_ridge_fit: every penalty must be finite and >= 0%s");
-  if (dtype == CVM_F64)
-    return ridge_fit_impl<double>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return ridge_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_ridge_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_ridge_fit", [&](auto t) {
+    return ridge_fit_impl<decltype(t)>(XTX, XTY, n_folds, K, M, lambdas, L, B, info, ws, ws_bytes, (hipStream_t)stream);
+  });
 }
 
 size_t cvm_lda_workspace_bytes(int64_t n_folds, int K, int C, int L) {
@@ -510,13 +505,10 @@ int cvm_lda_fit(const void *XTX, const void *XTY, const double *class_w, int64_t
   for (int l = 0; l < L; ++l)
     if (!(shrinkage[l] >= 0.0 && shrinkage[l] <= 1.0))
       return fail(CVM_EINVAL, "cvm_lda_fit: every shrinkage must lie in [0, 1]%s");
-  if (dtype == CVM_F64)
-    return lda_fit_impl<double>(XTX, XTY, class_w, n_folds, K, C, shrinkage, L, coef, intercept, info, ws, ws_bytes,
-                                (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return lda_fit_impl<float>(XTX, XTY, class_w, n_folds, K, C, shrinkage, L, coef, intercept, info, ws, ws_bytes,
-                               (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_lda_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_lda_fit", [&](auto t) {
+    return lda_fit_impl<decltype(t)>(XTX, XTY, class_w, n_folds, K, C, shrinkage, L, coef, intercept, info, ws, ws_bytes,
+                                     (hipStream_t)stream);
+  });
 }
 
 size_t cvm_enet_workspace_bytes(int64_t n_folds, int K, int M, int L) {
@@ -539,13 +531,10 @@ int cvm_enet_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M
     return fail(CVM_EINVAL, "cvm_enet_fit: 0 < l1_ratio <= 1 (l1_ratio = 0 is cvm_ridge_fit)%s");
   if (!(tol >= 1e-12 && tol < 1.0)) return fail(CVM_EINVAL, "cvm_enet_fit: 1e-12 <= tol < 1%s");
   if (max_sweeps < 1) return fail(CVM_EINVAL, "cvm_enet_fit: max_sweeps >= 1%s");
-  if (dtype == CVM_F64)
-    return enet_fit_impl<double>(XTX, XTY, n_folds, K, M, lambdas, L, l1_ratio, tol, max_sweeps, B, info, sweeps, ws,
-                                 ws_bytes, (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return enet_fit_impl<float>(XTX, XTY, n_folds, K, M, lambdas, L, l1_ratio, tol, max_sweeps, B, info, sweeps, ws,
-                                ws_bytes, (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_enet_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_enet_fit", [&](auto t) {
+    return enet_fit_impl<decltype(t)>(XTX, XTY, n_folds, K, M, lambdas, L, l1_ratio, tol, max_sweeps, B, info, sweeps, ws,
+                                      ws_bytes, (hipStream_t)stream);
+  });
 }
 
 size_t cvm_omp_workspace_bytes(int64_t n_folds, int K, int M, int A) {
@@ -563,13 +552,10 @@ int cvm_omp_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
   if (normalize != 0 && normalize != 1) return fail(CVM_EINVAL, "cvm_omp_fit: normalize must be 0 or 1%s");
   if (!(rank_tol < 1.0)) return fail(CVM_EINVAL, "cvm_omp_fit: rank_tol must be below 1 (<= 0: the default)%s");
   if (rank_tol <= 0.0) rank_tol = 32.0 * A * 0x1p-52;
-  if (dtype == CVM_F64)
-    return omp_fit_impl<double>(XTX, XTY, n_folds, K, M, A, normalize, rank_tol, B, support, n_fit, ws, ws_bytes,
-                                (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return omp_fit_impl<float>(XTX, XTY, n_folds, K, M, A, normalize, rank_tol, B, support, n_fit, ws, ws_bytes,
-                               (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_omp_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_omp_fit", [&](auto t) {
+    return omp_fit_impl<decltype(t)>(XTX, XTY, n_folds, K, M, A, normalize, rank_tol, B, support, n_fit, ws, ws_bytes,
+                                     (hipStream_t)stream);
+  });
 }
 
 size_t cvm_pcalda_workspace_bytes(int64_t n_folds, int K, int C, int A) {
@@ -591,11 +577,10 @@ int cvm_pcalda_fit(const void *V, const double *eigenvalues, const int32_t *n_co
   if (!V || !eigenvalues || !n_comp || !XTY || !class_w || !coef || !intercept || !n_fit || !info || !ws)
     return fail(CVM_EINVAL, "cvm_pcalda_fit: null pointer%s");
   if (pivot_tol <= 0.0) pivot_tol = PCL_PIVOT_TOL;
-  if (dtype == CVM_F64)
-    return pcalda_fit_impl<double>(V, eigenvalues, n_comp, XTY, class_w, n_folds, K, C, A, pivot_tol, coef, intercept,
-                                   n_fit, info, ws, ws_bytes, (hipStream_t)stream);
-  return pcalda_fit_impl<float>(V, eigenvalues, n_comp, XTY, class_w, n_folds, K, C, A, pivot_tol, coef, intercept,
-                                n_fit, info, ws, ws_bytes, (hipStream_t)stream);
+  return by_dtype(dtype, "cvm_pcalda_fit", [&](auto t) {
+    return pcalda_fit_impl<decltype(t)>(V, eigenvalues, n_comp, XTY, class_w, n_folds, K, C, A, pivot_tol, coef, intercept,
+                                        n_fit, info, ws, ws_bytes, (hipStream_t)stream);
+  });
 }
 
 size_t cvm_pcr_workspace_bytes(int64_t n_folds, int K, int M, int A) {
@@ -613,13 +598,10 @@ int cvm_pcr_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
     return fail(CVM_EINVAL, "cvm_pcr_fit: XTY and B go with M > 0, neither with M == 0 (PCA only)%s");
   if (!(rank_tol < 1.0)) return fail(CVM_EINVAL, "cvm_pcr_fit: rank_tol must be below 1 (<= 0: the default)%s");
   if (rank_tol <= 0.0) rank_tol = 32.0 * K * 0x1p-52;
-  if (dtype == CVM_F64)
-    return pcr_fit_impl<double>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
-                                (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return pcr_fit_impl<float>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
-                               (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_pcr_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_pcr_fit", [&](auto t) {
+    return pcr_fit_impl<decltype(t)>(XTX, XTY, n_folds, K, M, A, rank_tol, B, eigenvalues, V, n_fit, sweeps, ws, ws_bytes,
+                                     (hipStream_t)stream);
+  });
 }
 
 size_t cvm_pcr_blocked_workspace_bytes(int64_t n_folds, int K, int M, int A) {
@@ -639,13 +621,10 @@ int cvm_pcr_blocked_fit(const void *XTX, const void *XTY, int64_t n_folds, int K
   if (max_sweeps < 1 || max_sweeps > PCR_MAXSWEEPS)
     return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: max_sweeps must be 1 .. 60%s");
   if (rank_tol <= 0.0) rank_tol = 32.0 * K * 0x1p-52;
-  if (dtype == CVM_F64)
-    return pcr_blocked_fit_impl<double>(XTX, XTY, n_folds, K, M, A, rank_tol, max_sweeps, B, eigenvalues, V, n_fit,
-                                        sweeps, ws, ws_bytes, (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return pcr_blocked_fit_impl<float>(XTX, XTY, n_folds, K, M, A, rank_tol, max_sweeps, B, eigenvalues, V, n_fit,
-                                       sweeps, ws, ws_bytes, (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_pcr_blocked_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_pcr_blocked_fit", [&](auto t) {
+    return pcr_blocked_fit_impl<decltype(t)>(XTX, XTY, n_folds, K, M, A, rank_tol, max_sweeps, B, eigenvalues, V, n_fit,
+                                             sweeps, ws, ws_bytes, (hipStream_t)stream);
+  });
 }
 
 // shapes of cvm_cv_predict / cvm_cv_predict_plan: an error message, or nullptr
@@ -668,11 +647,10 @@ int cvm_cv_predict(const void *X, int64_t ldX, const int64_t *idx, const int64_t
   if (!X || !offsets || !B || !out) return fail(CVM_EINVAL, "cvm_cv_predict: null pointer%s");
   if (by_row != 0 && by_row != 1) return fail(CVM_EINVAL, "cvm_cv_predict: by_row must be 0 or 1%s");
   if (const char *bad = predict_bad_shape(n_folds, max_fold_rows, ldX, K, M, A, dtype)) return fail(CVM_EINVAL, bad);
-  if (dtype == CVM_F64)
-    return predict_impl<double>(X, ldX, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, out, by_row,
-                                (hipStream_t)stream);
-  return predict_impl<float>(X, ldX, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, out, by_row,
-                             (hipStream_t)stream);
+  return by_dtype(dtype, "cvm_cv_predict", [&](auto t) {
+    return predict_impl<decltype(t)>(X, ldX, idx, offsets, n_folds, max_fold_rows, K, M, A, muX, sdX, muY, sdY, B, out,
+                                     by_row, (hipStream_t)stream);
+  });
 }
 
 int cvm_cv_predict_plan(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int K, int M, int A, int dtype, int aligned,

@@ -3,9 +3,10 @@
 // G = XTX[f], h = XTY[f][:, m], rho = l1_ratio,
 //   minimise over beta:  1/2 beta' G beta - h' beta + lambda_l (rho |beta|_1 + 1/2 (1 - rho) |beta|_2^2)
 // by cyclic coordinate descent with covariance updates (g = h - G beta kept current by the row of G of every
-// coefficient that moves).  F x M independent penalty PATHS, one wavefront (a workgroup of 64 threads) per path:
-// the path walks its penalties from the largest down, each warm-started from the one before.  All arithmetic
-// in float64, inputs widened on load, B rounded once on store.
+// coefficient that moves).  F x M independent penalty PATHS, one wavefront (a workgroup of 64 threads) per path,
+// dealt to the workspace slots by slot_first (fit_plan.hpp): the path walks its penalties from the largest down,
+// each warm-started from the one before.  All arithmetic in float64, inputs widened on load, B rounded once on
+// store.
 //
 // Per path and penalty:
 //   * ACTIVE mode.  Up to 64 coordinates are active; lane i holds the index, coefficient, g and diagonal of
@@ -90,11 +91,7 @@ __global__ __launch_bounds__(64) void enet_kernel(const EnetArgs a) {
   const int lane = threadIdx.x;
   const unsigned long long below = (1ull << lane) - 1ull;
   const double rho = a.rho;
-  // as ridge_kernel: workgroups that share blockIdx % 8 take consecutive slots, so the responses of one fold
-  // (consecutive in the path order) run on one XCD and read XTX[f] from that XCD's L2 (speed only)
-  const int b = blockIdx.x;
-  int t = b >> 3;
-  for (int y = 0; y < (b & 7); ++y) t += (G - y + 7) >> 3;
+  const int b = blockIdx.x, t = slot_first(b, G);
   double *dg = a.ws + (size_t)b * a.per;
   const double nan = __builtin_nan("");
 
@@ -361,10 +358,7 @@ __global__ __launch_bounds__(64) void enet_kernel(const EnetArgs a) {
 
 // Workspace for full concurrency: min(F M, ENET_MAXWG) slots.  Host arithmetic only (no device query).
 size_t enet_workspace_bytes(int64_t F, int K, int M) {
-  int64_t P = F * (int64_t)M;
-  if (P < 1) P = 1;
-  if (P > ENET_MAXWG) P = ENET_MAXWG;
-  return (size_t)P * enet_path_bytes(K);
+  return slot_workspace_bytes(F * (int64_t)M, enet_path_bytes(K), ENET_MAXWG);
 }
 
 template <typename T>
@@ -372,8 +366,7 @@ int enet_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, con
                   double tol, int max_sweeps, void *B, int32_t *info, int32_t *sweeps, void *ws, size_t ws_bytes,
                   hipStream_t st) {
   const size_t per = enet_path_bytes(K);
-  const size_t fit = ws_bytes / per;
-  if (fit < 1) return fail(CVM_EWORKSPACE, "cvm_enet_fit: workspace too small for one path%s");
+  if (ws_bytes < per) return fail(CVM_EWORKSPACE, "cvm_enet_fit: workspace too small for one path%s");
   if (F == 0) return CVM_OK;
   EnetArgs a;
   memset(&a, 0, sizeof(a));
@@ -383,17 +376,15 @@ int enet_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, con
   a.per = per / 8;
   a.K = K; a.M = M; a.L = L; a.max_sweeps = max_sweeps;
   a.rho = rho; a.tol = tol;
-  int64_t G = a.P < (int64_t)fit ? a.P : (int64_t)fit;
-  if (G > ENET_MAXWG) G = ENET_MAXWG;
-  a.G = (int)G;
+  a.G = slot_count(a.P, per, ws_bytes, ENET_MAXWG);
   // largest penalty first; equal penalties in the caller's order
   for (int l = 0; l < L; ++l) a.order[l] = l;
   std::stable_sort(a.order, a.order + L, [&](int32_t x, int32_t y) { return lambdas[x] > lambdas[y]; });
   for (int l = 0; l < L; ++l) a.lam[l] = lambdas[a.order[l]];
   if (K <= ENET_SMALLK)
-    hipLaunchKernelGGL((enet_kernel<T, ENET_LDS_SMALL>), dim3((unsigned)G), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((enet_kernel<T, ENET_LDS_SMALL>), dim3((unsigned)a.G), dim3(64), 0, st, a);
   else
-    hipLaunchKernelGGL((enet_kernel<T, ENET_LDS_LARGE>), dim3((unsigned)G), dim3(64), 0, st, a);
+    hipLaunchKernelGGL((enet_kernel<T, ENET_LDS_LARGE>), dim3((unsigned)a.G), dim3(64), 0, st, a);
   HIP_OK(hipGetLastError());
   return CVM_OK;
 }

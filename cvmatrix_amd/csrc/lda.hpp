@@ -275,20 +275,11 @@ int lda_fit_impl(const void *XTX, const void *XTY, const double *class_w, int64_
   // folds per chunk: as many as run with every factorisation in flight, at least one; never more tiles or
   // (fold, g) pairs than a grid holds
   auto need = [&](int64_t n) { return lda_layout(n, K, C, L).ridge + ridge_workspace_bytes(n, K, C, L); };
-  int64_t nf = 1, top = F;
+  int64_t top = F;
   if (top > (int64_t)(0x40000000 / ntile)) top = 0x40000000 / ntile;
   if (top > (int64_t)(0x40000000 / L)) top = 0x40000000 / L;
-  if (top < 1) top = 1;
-  if (need(top) <= ws_bytes) {
-    nf = top;
-  } else {
-    int64_t lo = 1, hi = top;           // need(lo) may exceed ws_bytes: one fold then runs with fewer slots
-    while (hi - lo > 1) {
-      const int64_t mid = lo + (hi - lo) / 2;
-      if (need(mid) <= ws_bytes) lo = mid; else hi = mid;
-    }
-    nf = lo;
-  }
+  // (need(1) may exceed ws_bytes: one fold then runs with fewer ridge slots)
+  const int64_t nf = folds_per_chunk(top, ws_bytes, need);
   const LdaLayout o = lda_layout(nf, K, C, L);
   char *w = reinterpret_cast<char *>(ws);
   const size_t esz = sizeof(T);

@@ -8,8 +8,8 @@
 //      (no candidate, or nothing left to explain) ends the path
 //   4. w = L^-1 G[S, j], d^2 = G_jj - w'w extend the Cholesky factor L of G_SS; d^2 <= rank_tol G_jj ends the path
 //   5. L L' gamma = h_S;  B[f][a][:, m] = gamma scattered to S, exactly 0 elsewhere.
-// F x M independent PATHS, one wavefront (a workgroup of 64 threads) per path, dealt as enet_kernel deals its
-// paths.  All arithmetic in float64, inputs widened on load, B rounded once on store.
+// F x M independent PATHS, one wavefront (a workgroup of 64 threads) per path, dealt to the workspace
+// slots by slot_first (fit_plan.hpp).  All arithmetic in float64, inputs widened on load, B rounded once on store.
 //
 // Per path: lane i holds the index, gamma, z = (L^-1 h_S)_i and the diagonal L_ii of selected variable i in
 // registers.  The strict lower triangle of L (64 x 64) lies in LDS with a pitch of 65 doubles: the column read of
@@ -63,11 +63,7 @@ __global__ __launch_bounds__(64) void omp_kernel(const OmpArgs a) {
   const int K = a.K, M = a.M, A = a.A, G = a.G;
   const int lane = threadIdx.x;
   const bool normalize = a.normalize != 0;
-  // as enet_kernel: workgroups that share blockIdx % 8 take consecutive paths, so the responses of one fold run on
-  // one XCD and read XTX[f] from that XCD's L2 (speed only)
-  const int b = blockIdx.x;
-  int t = b >> 3;
-  for (int y = 0; y < (b & 7); ++y) t += (G - y + 7) >> 3;
+  const int b = blockIdx.x, t = slot_first(b, G);
   double *scale = a.ws + (size_t)b * a.per;
   const double nan = __builtin_nan("");
 
@@ -188,18 +184,14 @@ __global__ __launch_bounds__(64) void omp_kernel(const OmpArgs a) {
 
 // Workspace for full concurrency: min(F M, OMP_MAXWG) slots.  Host arithmetic only (no device query).
 size_t omp_workspace_bytes(int64_t F, int K, int M) {
-  int64_t P = F * (int64_t)M;
-  if (P < 1) P = 1;
-  if (P > OMP_MAXWG) P = OMP_MAXWG;
-  return (size_t)P * omp_path_bytes(K);
+  return slot_workspace_bytes(F * (int64_t)M, omp_path_bytes(K), OMP_MAXWG);
 }
 
 template <typename T>
 int omp_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, int A, int normalize, double rank_tol,
                  void *B, int32_t *support, int32_t *n_fit, void *ws, size_t ws_bytes, hipStream_t st) {
   const size_t per = omp_path_bytes(K);
-  const size_t fit = ws_bytes / per;
-  if (fit < 1) return fail(CVM_EWORKSPACE, "cvm_omp_fit: workspace too small for one path%s");
+  if (ws_bytes < per) return fail(CVM_EWORKSPACE, "cvm_omp_fit: workspace too small for one path%s");
   if (F == 0) return CVM_OK;
   OmpArgs a;
   memset(&a, 0, sizeof(a));
@@ -209,10 +201,8 @@ int omp_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, int 
   a.per = per / 8;
   a.K = K; a.M = M; a.A = A; a.normalize = normalize;
   a.rank_tol = rank_tol;
-  int64_t G = a.P < (int64_t)fit ? a.P : (int64_t)fit;
-  if (G > OMP_MAXWG) G = OMP_MAXWG;
-  a.G = (int)G;
-  hipLaunchKernelGGL((omp_kernel<T>), dim3((unsigned)G), dim3(64), 0, st, a);
+  a.G = slot_count(a.P, per, ws_bytes, OMP_MAXWG);
+  hipLaunchKernelGGL((omp_kernel<T>), dim3((unsigned)a.G), dim3(64), 0, st, a);
   HIP_OK(hipGetLastError());
   return CVM_OK;
 }

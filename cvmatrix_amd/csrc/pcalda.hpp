@@ -382,15 +382,7 @@ int pcalda_fit_impl(const void *V, const double *eig, const int32_t *n_comp, con
   int64_t top = F;
   const int64_t per = NS > ntile ? NS : ntile;
   if (top > (int64_t)(0x40000000 / per)) top = 0x40000000 / per;
-  int64_t nf = top;
-  if (pcl_layout(top, K, C, A).end > ws_bytes) {
-    int64_t lo = 1, hi = top;
-    while (hi - lo > 1) {
-      const int64_t mid = lo + (hi - lo) / 2;
-      if (pcl_layout(mid, K, C, A).end <= ws_bytes) lo = mid; else hi = mid;
-    }
-    nf = lo;
-  }
+  const int64_t nf = folds_per_chunk(top, ws_bytes, [&](int64_t n) { return pcl_layout(n, K, C, A).end; });
   const size_t lds = pcl_factor_lds(C, A);
   HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(pcalda_factor_kernel<T>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

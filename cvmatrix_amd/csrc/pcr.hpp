@@ -334,17 +334,14 @@ __global__ __launch_bounds__(PCR_THREADS) void pcr_kernel(const PcrArgs a) {
 
 // Workspace for full concurrency: min(F, PCR_MAXWG) slots.  Host arithmetic only (no device query).
 size_t pcr_workspace_bytes(int64_t F, int K, int M) {
-  if (F < 1) F = 1;
-  if (F > PCR_MAXWG) F = PCR_MAXWG;
-  return (size_t)F * pcr_slot_bytes(K, M);
+  return slot_workspace_bytes(F, pcr_slot_bytes(K, M), PCR_MAXWG);
 }
 
 template <typename T>
 int pcr_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, int A, double rank_tol, void *B,
                  double *eig, void *V, int32_t *n_fit, int32_t *sweeps, void *ws, size_t ws_bytes, hipStream_t st) {
   const size_t per = pcr_slot_bytes(K, M);
-  const size_t fit = ws_bytes / per;
-  if (fit < 1) return fail(CVM_EWORKSPACE, "cvm_pcr_fit: workspace too small for one fold%s");
+  if (ws_bytes < per) return fail(CVM_EWORKSPACE, "cvm_pcr_fit: workspace too small for one fold%s");
   if (F == 0) return CVM_OK;
   PcrArgs a;
   memset(&a, 0, sizeof(a));
@@ -354,10 +351,8 @@ int pcr_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, int 
   a.per = per / 8;
   a.rank_tol = rank_tol;
   a.K = K; a.M = M; a.A = A; a.ld = pcr_ld(K, M);
-  int64_t G = F < (int64_t)fit ? F : (int64_t)fit;
-  if (G > PCR_MAXWG) G = PCR_MAXWG;
-  a.G = (int)G;
-  hipLaunchKernelGGL(pcr_kernel<T>, dim3((unsigned)G), dim3(PCR_THREADS), 0, st, a);
+  a.G = slot_count(F, per, ws_bytes, PCR_MAXWG);
+  hipLaunchKernelGGL(pcr_kernel<T>, dim3((unsigned)a.G), dim3(PCR_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
   return CVM_OK;
 }

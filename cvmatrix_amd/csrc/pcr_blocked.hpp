@@ -60,12 +60,28 @@ __host__ __device__ inline int pcrb_m(int K) {
 }
 // a slot: S, V (Kp x Kp), h matrices Q (64 x 64), the coefficient sum (K x M), the signs (Kp), the threshold,
 // then int32: the ordering (Kp), "pair rotated in this round" (h), the fold's words, the batch's status array
-// (PCRB_MAXSLOTS, used in slot 0 only)
+// (PCRB_MAXSLOTS, used in slot 0 only).  The one statement of that layout, as byte offsets (S at 0): the slot's
+// size, the kernels' pointers and the host's read of the status array all come from it.
+struct PcrbLayout {
+  size_t V, Q, acc, sgn, thr, ord, rot, word, status, end;
+};
+__host__ __device__ inline PcrbLayout pcrb_layout(int K, int M, int Kp, int h) {
+  PcrbLayout o;
+  o.V = (size_t)Kp * Kp * 8;
+  o.Q = 2 * o.V;
+  o.acc = o.Q + (size_t)h * PCRB_TILE * PCRB_TILE * 8;
+  o.sgn = o.acc + (size_t)K * M * 8;
+  o.thr = o.sgn + (size_t)Kp * 8;
+  o.ord = o.thr + 2 * 8;
+  o.rot = o.ord + (size_t)Kp * 4;
+  o.word = o.rot + (size_t)h * 4;
+  o.status = o.word + PCRB_WORDS * 4;
+  o.end = o.status + PCRB_MAXSLOTS * 4;
+  return o;
+}
 inline size_t pcrb_slot_bytes(int K, int M) {
-  const size_t m = pcrb_m(K), Kp = m * PCRB_BLOCK, h = m / 2;
-  const size_t d = 2 * Kp * Kp + h * PCRB_TILE * PCRB_TILE + (size_t)K * M + Kp + 2;
-  const size_t i = Kp + h + PCRB_WORDS + PCRB_MAXSLOTS;
-  return align_up(d * 8 + i * 4, 256);
+  const int m = pcrb_m(K);
+  return align_up(pcrb_layout(K, M, m * PCRB_BLOCK, m / 2).end, 256);
 }
 
 struct PcrbSlot {
@@ -73,19 +89,11 @@ struct PcrbSlot {
   int *ord, *rot, *word, *status;
 };
 __device__ inline PcrbSlot pcrb_slot(const PcrbArgs &a, int g) {
-  PcrbSlot s;
-  const size_t kk = (size_t)a.Kp * a.Kp;
-  s.S = reinterpret_cast<double *>(a.ws + (size_t)g * a.per);
-  s.V = s.S + kk;
-  s.Q = s.V + kk;
-  s.acc = s.Q + (size_t)a.h * PCRB_TILE * PCRB_TILE;
-  s.sgn = s.acc + (size_t)a.K * a.M;
-  s.thr = s.sgn + a.Kp;
-  s.ord = reinterpret_cast<int *>(s.thr + 2);
-  s.rot = s.ord + a.Kp;
-  s.word = s.rot + a.h;
-  s.status = s.word + PCRB_WORDS;
-  return s;
+  const PcrbLayout o = pcrb_layout(a.K, a.M, a.Kp, a.h);
+  char *p = a.ws + (size_t)g * a.per;
+  auto d = [p](size_t off) { return reinterpret_cast<double *>(p + off); };
+  auto i = [p](size_t off) { return reinterpret_cast<int *>(p + off); };
+  return PcrbSlot{d(0), d(o.V), d(o.Q), d(o.acc), d(o.sgn), d(o.thr), i(o.ord), i(o.rot), i(o.word), i(o.status)};
 }
 
 // pair i of round r among m players, the round-robin order of pcr_kernel: p < q
@@ -404,9 +412,7 @@ __global__ __launch_bounds__(PCRB_THREADS) void pcrb_finish_kernel(const PcrbArg
 
 // min(F, PCRB_MAXSLOTS) slots.  Host arithmetic only (no device query).
 size_t pcr_blocked_workspace_bytes(int64_t F, int K, int M) {
-  if (F < 1) F = 1;
-  if (F > PCRB_MAXSLOTS) F = PCRB_MAXSLOTS;
-  return (size_t)F * pcrb_slot_bytes(K, M);
+  return slot_workspace_bytes(F, pcrb_slot_bytes(K, M), PCRB_MAXSLOTS);
 }
 
 template <typename T>
@@ -414,8 +420,7 @@ int pcr_blocked_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int
                          int max_sweeps, void *B, double *eig, void *V, int32_t *n_fit, int32_t *sweeps, void *ws,
                          size_t ws_bytes, hipStream_t st) {
   const size_t per = pcrb_slot_bytes(K, M);
-  const size_t fit = ws_bytes / per;
-  if (fit < 1) return fail(CVM_EWORKSPACE, "cvm_pcr_blocked_fit: workspace too small for one fold%s");
+  if (ws_bytes < per) return fail(CVM_EWORKSPACE, "cvm_pcr_blocked_fit: workspace too small for one fold%s");
   if (F == 0) return CVM_OK;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
@@ -434,8 +439,9 @@ int pcr_blocked_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int
   a.rank_tol = rank_tol;
   const int m = pcrb_m(K), h = m / 2;
   a.K = K; a.M = M; a.A = A; a.Kp = m * PCRB_BLOCK; a.h = h;
-  int64_t cap = F < (int64_t)fit ? F : (int64_t)fit;
-  if (cap > PCRB_MAXSLOTS) cap = PCRB_MAXSLOTS;
+  const int64_t cap = slot_count(F, per, ws_bytes, PCRB_MAXSLOTS);
+  // where the collect kernel leaves the status array: in slot 0
+  const size_t off = pcrb_layout(K, M, a.Kp, h).status;
   const unsigned tiles = (unsigned)(h * (h - 1) / 2 + h * h);
   std::vector<int> status((size_t)cap);
   for (int64_t f0 = 0; f0 < F; f0 += cap) {
@@ -444,10 +450,6 @@ int pcr_blocked_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int
     a.G = G;
     hipLaunchKernelGGL(pcrb_init_kernel<T>, dim3((unsigned)G, (unsigned)h), dim3(PCRB_THREADS), 0, st, a);
     HIP_OK(hipGetLastError());
-    // where the collect kernel leaves the status array: slot 0, behind the ordering, the round's words and the fold's
-    const size_t kk = (size_t)a.Kp * a.Kp;
-    const size_t off = (2 * kk + (size_t)h * PCRB_TILE * PCRB_TILE + (size_t)K * M + a.Kp + 2) * 8 +
-                       ((size_t)a.Kp + h + PCRB_WORDS) * 4;
     int left = G;
     for (int sweep = 1; sweep <= max_sweeps && left > 0; ++sweep) {
       for (int r = 0; r < m - 1; ++r) {

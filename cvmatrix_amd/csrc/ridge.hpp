@@ -1,7 +1,8 @@
 // ridge.hpp -- part of libcvmhip.so (included by cvmhip.hip inside its anonymous namespace, after pls.hpp).
 // Ridge regression over a grid of penalties for every fold: for fold f and penalty l,
 //   (XTX[f] + lambda_l I) B[f][l] = XTY[f]
-// F x L independent SPD problems of order K with M right-hand sides, one persistent workgroup per problem.
+// F x L independent SPD problems of order K with M right-hand sides, one persistent workgroup per workspace slot,
+// the problems dealt to the slots by slot_first (fit_plan.hpp).
 //
 // Per problem (all arithmetic in float64, inputs widened on load, B rounded once on store):
 //   * blocked left-looking Cholesky of the augmented K + M rows [XTX + lambda I ; XTY^T]: its last M rows
@@ -51,11 +52,7 @@ __global__ __launch_bounds__(RIDGE_THREADS) void ridge_kernel(const RidgeArgs a)
   const int R = K + M;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 15, sub = lane >> 4;
-  // workgroups that share blockIdx % 8 take consecutive slots, so the problems of one fold (consecutive in
-  // the problem order) run on blocks of one XCD and read XTX[f] from that XCD's L2 (speed only)
-  const int b = blockIdx.x;
-  int t = b >> 3;
-  for (int y = 0; y < (b & 7); ++y) t += (G - y + 7) >> 3;
+  const int b = blockIdx.x, t = slot_first(b, G);
   double *W = a.ws + (size_t)b * a.per;
 
   for (int64_t s = t; s < a.P; s += G) {
@@ -269,18 +266,14 @@ __global__ __launch_bounds__(RIDGE_THREADS) void ridge_kernel(const RidgeArgs a)
 
 // Workspace for full concurrency: min(F L, RIDGE_MAXWG) slots.  Host arithmetic only (no device query).
 size_t ridge_workspace_bytes(int64_t F, int K, int M, int L) {
-  int64_t P = F * (int64_t)L;
-  if (P < 1) P = 1;
-  if (P > RIDGE_MAXWG) P = RIDGE_MAXWG;
-  return (size_t)P * ridge_problem_bytes(K, M);
+  return slot_workspace_bytes(F * (int64_t)L, ridge_problem_bytes(K, M), RIDGE_MAXWG);
 }
 
 template <typename T>
 int ridge_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, const double *lambdas, int L, void *B,
                    int32_t *info, void *ws, size_t ws_bytes, hipStream_t st) {
   const size_t per = ridge_problem_bytes(K, M);
-  const size_t fit = ws_bytes / per;
-  if (fit < 1) return fail(CVM_EWORKSPACE, "cvm_ridge_fit: workspace too small for one problem%s");
+  if (ws_bytes < per) return fail(CVM_EWORKSPACE, "cvm_ridge_fit: workspace too small for one problem%s");
   if (F == 0) return CVM_OK;
   RidgeArgs a;
   memset(&a, 0, sizeof(a));
@@ -289,11 +282,9 @@ int ridge_fit_impl(const void *XTX, const void *XTY, int64_t F, int K, int M, co
   a.P = F * (int64_t)L;
   a.per = per / 8;
   a.K = K; a.M = M; a.L = L; a.ld = ridge_ld(K, M);
-  int64_t G = a.P < (int64_t)fit ? a.P : (int64_t)fit;
-  if (G > RIDGE_MAXWG) G = RIDGE_MAXWG;
-  a.G = (int)G;
+  a.G = slot_count(a.P, per, ws_bytes, RIDGE_MAXWG);
   for (int l = 0; l < L; ++l) a.lambdas[l] = lambdas[l];
-  hipLaunchKernelGGL(ridge_kernel<T>, dim3((unsigned)G), dim3(RIDGE_THREADS), 0, st, a);
+  hipLaunchKernelGGL(ridge_kernel<T>, dim3((unsigned)a.G), dim3(RIDGE_THREADS), 0, st, a);
   HIP_OK(hipGetLastError());
   return CVM_OK;
 }

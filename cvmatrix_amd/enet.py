@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import dtype_code, launch, training_pair
+from ._stage import check_fit_dims, check_grid, dtype_code, launch, training_pair
 
 MAX_K = 4096
 MAX_RESPONSES = 64
@@ -48,14 +48,7 @@ class EnetConvergenceWarning(RuntimeWarning):
 
 def check_lambdas(lambdas) -> np.ndarray:
     """The penalty grid as a contiguous 1-D float64 array: 1 to 256 values, each finite and > 0."""
-    lam = np.asarray(lambdas, dtype=np.float64)
-    if lam.ndim != 1:
-        raise ValueError(f"lambdas must be one-dimensional, got shape {lam.shape}.")
-    if not 1 <= lam.size <= MAX_PENALTIES:
-        raise ValueError(f"lambdas must hold 1 to {MAX_PENALTIES} values, got {lam.size}.")
-    if not np.all(np.isfinite(lam)) or np.any(lam <= 0):
-        raise ValueError("every lambda must be finite and > 0.")
-    return np.ascontiguousarray(lam)
+    return check_grid("lambdas", lambdas, MAX_PENALTIES, low_open=True)
 
 
 def check_solver_arguments(l1_ratio, tol, max_sweeps):
@@ -88,10 +81,7 @@ def enet_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, lambdas, l1_ratio: fl
     lam = check_lambdas(lambdas)
     l1_ratio, tol, max_sweeps = check_solver_arguments(l1_ratio, tol, max_sweeps)
     XTX, XTY, F, K, M = training_pair("enet_fit_batched", XTX, XTY)
-    if not 1 <= K <= MAX_K:
-        raise ValueError(f"The device elastic net takes 1 <= K <= {MAX_K}.")
-    if not 1 <= M <= MAX_RESPONSES:
-        raise ValueError(f"The device elastic net takes 1 to {MAX_RESPONSES} responses.")
+    check_fit_dims("The device elastic net", K, M, MAX_K, MAX_RESPONSES)
     L = lam.size
     dev = XTX.device
     B = torch.empty((F, L, K, M), dtype=XTX.dtype, device=dev)

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import dtype_code, launch, training_pair
+from ._stage import check_grid, dtype_code, launch, training_pair
 from .predict import cv_predict
 
 MAX_K = 4096
@@ -45,16 +45,7 @@ class LDAFit(NamedTuple):
 
 def check_shrinkage(shrinkage) -> np.ndarray:
     """The shrinkage grid as a contiguous 1-D float64 array: a scalar or 1 to 256 values, each in [0, 1]."""
-    g = np.asarray(shrinkage, dtype=np.float64)
-    if g.ndim == 0:
-        g = g.reshape(1)
-    if g.ndim != 1:
-        raise ValueError(f"shrinkage must be a scalar or one-dimensional, got shape {g.shape}.")
-    if not 1 <= g.size <= MAX_SHRINKAGES:
-        raise ValueError(f"shrinkage must hold 1 to {MAX_SHRINKAGES} values, got {g.size}.")
-    if not np.all((g >= 0) & (g <= 1)):           # (NaN fails both comparisons)
-        raise ValueError("every shrinkage must lie in [0, 1].")
-    return np.ascontiguousarray(g)
+    return check_grid("shrinkage", shrinkage, MAX_SHRINKAGES, low_open=False, high=1, scalar_ok=True)
 
 
 def check_dims(K: int, C: int) -> None:

@@ -12,7 +12,6 @@ cross-validated RMSE per number of variables.  No CPU fallback."""
 
 from __future__ import annotations
 
-import math
 import warnings
 from typing import NamedTuple, Optional
 
@@ -20,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import dtype_code, launch, training_pair
+from ._stage import check_count, check_fit_dims, check_tolerance, dtype_code, launch, training_pair
 
 MAX_K = 4096
 MAX_RESPONSES = 64
@@ -52,20 +51,13 @@ def default_rank_tol(A: int) -> float:
 
 def check_rank_tol(rank_tol) -> float:
     """None or a value <= 0: 0.0 (the library's default); otherwise a float below 1."""
-    if rank_tol is None:
-        return 0.0
-    tol = float(rank_tol)
-    if math.isnan(tol) or tol >= 1.0:
-        raise ValueError(f"rank_tol must be below 1, got {rank_tol!r}.")
-    return max(tol, 0.0)
+    return check_tolerance("rank_tol", rank_tol)
 
 
 def check_selected(A, K: int) -> int:
     """The number of variables to select as an int: an integer with 1 <= A <= min(K, 64)."""
     top = min(K, MAX_SELECTED)
-    if isinstance(A, bool) or not isinstance(A, (int, np.integer)) or not 1 <= A <= top:
-        raise ValueError(f"n_nonzero must be an integer with 1 <= n_nonzero <= min(K, {MAX_SELECTED}) = {top}, got {A!r}.")
-    return int(A)
+    return check_count("n_nonzero", A, top, f"min(K, {MAX_SELECTED}) = {top}")
 
 
 def omp_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, n_nonzero: int, *, normalize: bool = False,
@@ -84,10 +76,7 @@ def omp_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, n_nonzero: int, *, nor
     check_selected(n_nonzero, MAX_K)          # (what can be refused without the shapes is refused first)
     tol = check_rank_tol(rank_tol)
     XTX, XTY, F, K, M = training_pair("omp_fit_batched", XTX, XTY)
-    if not 1 <= K <= MAX_K:
-        raise ValueError(f"The device OMP takes 1 <= K <= {MAX_K}.")
-    if not 1 <= M <= MAX_RESPONSES:
-        raise ValueError(f"The device OMP takes 1 to {MAX_RESPONSES} responses.")
+    check_fit_dims("The device OMP", K, M, MAX_K, MAX_RESPONSES)
     A = check_selected(n_nonzero, K)
     dev = XTX.device
     B = torch.empty((F, A, K, M), dtype=XTX.dtype, device=dev)

@@ -18,14 +18,13 @@ components in place of shrinkages.  No row of X is read to fit the models.  No C
 
 from __future__ import annotations
 
-import math
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._stage import dtype_code, launch, training_pair
+from ._stage import check_count, check_tolerance, dtype_code, launch, training_pair
 from .lda import MAX_CLASSES, MIN_CLASSES, check_class_weights, training_class_weights
 from .pcr import MAX_K as MAX_K_SCALAR, MAX_K_BLOCKED, SOLVERS, pcr_fit_batched
 
@@ -56,21 +55,13 @@ class PCALDAFit(NamedTuple):
 
 def check_pivot_tol(pivot_tol) -> float:
     """None or a value <= 0: 0.0 (the library's default, 2^-26); otherwise a float below 1."""
-    if pivot_tol is None:
-        return 0.0
-    tol = float(pivot_tol)
-    if math.isnan(tol) or tol >= 1.0:
-        raise ValueError(f"pivot_tol must be below 1, got {pivot_tol!r}.")
-    return max(tol, 0.0)
+    return check_tolerance("pivot_tol", pivot_tol)
 
 
 def check_components(A, K: Optional[int] = None) -> int:
     """The number of components as an int: an integer with 1 <= A <= min(K, 64) (K None: 1 <= A <= 64)."""
     top = MAX_COMPONENTS if K is None else min(K, MAX_COMPONENTS)
-    if isinstance(A, bool) or not isinstance(A, (int, np.integer)) or not 1 <= A <= top:
-        raise ValueError(f"A must be an integer with 1 <= A <= min(K, {MAX_COMPONENTS})"
-                         + ("" if K is None else f" = {top}") + f", got {A!r}.")
-    return int(A)
+    return check_count("A", A, top, f"min(K, {MAX_COMPONENTS})" + ("" if K is None else f" = {top}"))
 
 
 def check_dims(K: int, C: int, A, limit: int = MAX_K) -> int:

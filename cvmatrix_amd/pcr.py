@@ -10,14 +10,13 @@ fit.B)`` and ``cv_rmse`` give the cross-validated RMSE per number of components.
 
 from __future__ import annotations
 
-import math
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._stage import dtype_code, launch, training_pair
+from ._stage import check_count, check_tolerance, dtype_code, launch, training_pair
 
 MAX_K = 512
 MAX_K_BLOCKED = 4096          # solver="blocked"
@@ -51,19 +50,12 @@ def default_rank_tol(K: int) -> float:
 
 def check_rank_tol(rank_tol) -> float:
     """None or a value <= 0: 0.0 (the library's default); otherwise a float below 1."""
-    if rank_tol is None:
-        return 0.0
-    tol = float(rank_tol)
-    if math.isnan(tol) or tol >= 1.0:
-        raise ValueError(f"rank_tol must be below 1, got {rank_tol!r}.")
-    return max(tol, 0.0)
+    return check_tolerance("rank_tol", rank_tol)
 
 
 def check_components(A, K: int) -> int:
     """The number of components as an int: an integer with 1 <= A <= K."""
-    if isinstance(A, bool) or not isinstance(A, (int, np.integer)) or not 1 <= A <= K:
-        raise ValueError(f"A must be an integer with 1 <= A <= K = {K}, got {A!r}.")
-    return int(A)
+    return check_count("A", A, K, f"K = {K}")
 
 
 def pcr_fit_batched(XTX: torch.Tensor, XTY: Optional[torch.Tensor], A: int, *, return_components: bool = False,
@@ -90,9 +82,7 @@ def pcr_fit_batched(XTX: torch.Tensor, XTY: Optional[torch.Tensor], A: int, *, r
         max_sweeps = MAX_SWEEPS
     elif not blocked:
         raise ValueError("max_sweeps goes with solver='blocked' (the scalar solver always allows 60).")
-    if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, (int, np.integer)) or not 1 <= max_sweeps <= MAX_SWEEPS:
-        raise ValueError(f"max_sweeps must be an integer with 1 <= max_sweeps <= {MAX_SWEEPS}, got {max_sweeps!r}.")
-    max_sweeps = int(max_sweeps)
+    max_sweeps = check_count("max_sweeps", max_sweeps, MAX_SWEEPS, str(MAX_SWEEPS))
     limit = MAX_K_BLOCKED if blocked else MAX_K
     hint = "" if blocked else f" (solver='blocked' takes K up to {MAX_K_BLOCKED})"
     # (the order is a rule of the solver, not of the tensors: it is refused wherever the matrix lives)

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._stage import dtype_code, launch, training_pair
+from ._stage import check_fit_dims, check_grid, dtype_code, launch, training_pair
 
 MAX_K = 4096
 MAX_RESPONSES = 64
@@ -33,14 +33,7 @@ class RidgeFit(NamedTuple):
 
 def check_lambdas(lambdas) -> np.ndarray:
     """The penalty grid as a contiguous 1-D float64 array: 1 to 256 values, each finite and >= 0."""
-    lam = np.asarray(lambdas, dtype=np.float64)
-    if lam.ndim != 1:
-        raise ValueError(f"lambdas must be one-dimensional, got shape {lam.shape}.")
-    if not 1 <= lam.size <= MAX_PENALTIES:
-        raise ValueError(f"lambdas must hold 1 to {MAX_PENALTIES} values, got {lam.size}.")
-    if not np.all(np.isfinite(lam)) or np.any(lam < 0):
-        raise ValueError("every lambda must be finite and >= 0.")
-    return np.ascontiguousarray(lam)
+    return check_grid("lambdas", lambdas, MAX_PENALTIES, low_open=False)
 
 
 def ridge_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, lambdas, *, check: bool = False) -> RidgeFit:
@@ -52,10 +45,7 @@ def ridge_fit_batched(XTX: torch.Tensor, XTY: torch.Tensor, lambdas, *, check: b
     raises ``numpy.linalg.LinAlgError`` naming the first (fold, lambda, pivot) whose matrix was not
     positive definite."""
     XTX, XTY, F, K, M = training_pair("ridge_fit_batched", XTX, XTY)
-    if not 1 <= K <= MAX_K:
-        raise ValueError(f"The device ridge takes 1 <= K <= {MAX_K}.")
-    if not 1 <= M <= MAX_RESPONSES:
-        raise ValueError(f"The device ridge takes 1 to {MAX_RESPONSES} responses.")
+    check_fit_dims("The device ridge", K, M, MAX_K, MAX_RESPONSES)
     lam = check_lambdas(lambdas)
     L = lam.size
     dev = XTX.device
