@@ -138,28 +138,39 @@ __device__ __forceinline__ double lane_value(double v, int j) {
 
 // One column of one fold: training-set mean and std from the fold's column sums (sv, qv), the
 // full-data sums (gs, gq), the training-set weight sum and divisor; reference operation order
-// (cvmatrix.py:1020, 1043, 1119-1128).  Writes the fold's statistics vector and the outputs.
-template <typename T>
-__device__ __forceinline__ void fold_column_finish(const FinArgs &a, int f, bool isX, int cc, double sv, double qv,
-                                                   double gs, double gq, double swt, double divisor,
-                                                   bool want_sd, double *fs) {
-  const int K = a.g.K, M = a.g.M;
+// (cvmatrix.py:1020, 1043, 1119-1128).
+__device__ __forceinline__ void column_mean_std(double sv, double qv, double gs, double gq, double swt, double divisor,
+                                                bool want_sd, double resolution, double &mu, double &sd) {
   const double st_ = gs - sv;          // cvmatrix.py:1020
-  const double mu = st_ / swt;         // cvmatrix.py:1043
-  double sd = 1.0;
+  mu = st_ / swt;                      // cvmatrix.py:1043
+  sd = 1.0;
   if (want_sd) {
     const double qt = gq - qv;
     double var = (-2 * mu * st_ + swt * (mu * mu) + qt) / divisor;   // 1119-1123
     var = (var < 0) ? 0.0 : var;       // np.maximum(var, 0): NaN stays NaN
     sd = sqrt(var);
-    if (sd <= a.resolution) sd = 1.0;  // 1128
+    if (sd <= resolution) sd = 1.0;    // 1128
   }
+}
+// The fold's statistics vector and the statistics outputs of that column.
+template <typename T>
+__device__ __forceinline__ void fold_column_store(const FinArgs &a, int f, bool isX, int cc, double mu, double sd,
+                                                  bool want_sd, double *fs) {
+  const int K = a.g.K, M = a.g.M;
   fs[isX ? cc : 2 * K + cc] = mu;
   fs[isX ? K + cc : 2 * K + M + cc] = 1.0 / sd;     // the finish MULTIPLIES by reciprocal stds (below)
   T *omu = (T *)(isX ? a.out_muX : a.out_muY), *osd = (T *)(isX ? a.out_sdX : a.out_sdY);
   const size_t o = (size_t)(a.seg0 + f) * (isX ? K : M) + cc;
   if (omu) omu[o] = (T)mu;
   if (osd && want_sd) osd[o] = (T)sd;
+}
+template <typename T>
+__device__ __forceinline__ void fold_column_finish(const FinArgs &a, int f, bool isX, int cc, double sv, double qv,
+                                                   double gs, double gq, double swt, double divisor,
+                                                   bool want_sd, double *fs) {
+  double mu, sd;
+  column_mean_std(sv, qv, gs, gq, swt, divisor, want_sd, a.resolution, mu, sd);
+  fold_column_store<T>(a, f, isX, cc, mu, sd, want_sd, fs);
 }
 
 // The same arithmetic for workgroups that derive the statistics they need themselves
@@ -199,16 +210,7 @@ __device__ __forceinline__ void inline_column_stat(const FinArgs &a, int f, bool
   }
   const double gs = isX ? a.gstats[cc] : a.gstats[2 * K + cc];
   const double gq = isX ? a.gstats[K + cc] : a.gstats[2 * K + M + cc];
-  const double st_ = gs - sv;          // cvmatrix.py:1020
-  mu = st_ / swt;                      // cvmatrix.py:1043
-  sd = 1.0;
-  if (want_sd) {
-    const double qt = gq - qv;
-    double var = (-2 * mu * st_ + swt * (mu * mu) + qt) / divisor;   // 1119-1123
-    var = (var < 0) ? 0.0 : var;
-    sd = sqrt(var);
-    if (sd <= a.resolution) sd = 1.0;  // 1128
-  }
+  column_mean_std(sv, qv, gs, gq, swt, divisor, want_sd, a.resolution, mu, sd);
   isd = 1.0 / sd;
 }
 
@@ -971,115 +973,251 @@ __global__ __launch_bounds__(FIT_THREADS) void fit_apply_kernel(const FinArgs a)
   }
 }
 
-
 // ----------------------------------------------------------------------------------
-// One-sweep path with few folds (<= SWF_MAX), everything in two launches after the Gram kernel:
-//   sweep_stats_kernel   full-data column sums (gstats) AND every fold's statistics
-//   sweep_finish4_kernel full-data G, H AND every fold's training matrices, each partial read once
+// One-sweep path with few folds (<= SWF_MAX), everything in ONE launch after the Gram kernel:
+//   sweep_finalize_kernel  full-data column sums (gstats), every fold's statistics, full-data G, H AND every
+//                          fold's training matrices, each partial read once
 // (fit_apply_kernel + fold_stats_kernel + apply_kernel read the folds' partials twice: 68 MB of the
 // 91 MB they move at C3.)  A fold's raw update U_f = sum_sp partial (float64); G = sum_f U_f in
 // fold order -- the very sums fit_apply_kernel and apply_kernel form, so the results are
 // bit-identical to cvm_sweep_fit + cvm_sweep_folds.
+//
+// The launch is a list of entries, one workgroup each, none empty, the heavier ones first:
+//   1. the blocks (SWF_R rows x PPR 16-byte pieces) of the DIAGONAL 128 x 128 tiles that hold elements on or above
+//      the diagonal (s_diag partials per fold),
+//   2. the blocks of the tiles above the diagonal, block row by block row (s_off partials per fold),
+//   3. XTY: rectangles of rows x Y columns, SWF4_YE elements each.
+// No workgroup depends on another: each forms the fold statistics of the columns it touches itself, from the
+// partials' column sums (0.6 MB at C3: they stay in L2), with the chains fold_stats_kernel runs (and sweep_stats_kernel ran) -- the fold's sums over
+// its s_diag partials in split order, the full-data sums over the folds in fold order, column_mean_std -- so
+// every number has the bits the separate kernels give it.  What later calls read is written by ONE designated
+// entry each: an X column's gstats / fstats / out_muX / out_sdX by the block of its row that holds the diagonal, a
+// Y column's by the XTY entry of its chunk with the first rows, the totals (sw, nz, neg_flag, out_fold) by entry 0.
 // ----------------------------------------------------------------------------------
 constexpr int SWF_MAX = 16;    // folds of the one-sweep path at most
-constexpr int SWF_R = 16;      // block rows of sweep_finish4_kernel
+constexpr int SWF_R = 16;      // block rows of sweep_finalize_kernel
+// PPR = 16-byte pieces per block row: 8 (16 rows x 128 bytes, 512 threads, 528 blocks at K = 512: up to three workgroups
+// per CU, SWF_WPE below, so that one's loads overlap another's stores) rather than 16 (blocks of 16 rows x 256 bytes, 1024 threads, 272
+// blocks).
+constexpr int SWF4_FG = 4;
+constexpr int SWF4_PPR = 8;
+template <int PPR> constexpr int swf4_threads() { return 16 * PPR * SWF4_FG; }
+template <int PPR> constexpr int swf4_ye() { return 16 * PPR; }     // XTY elements per entry (x SWF4_FG fold groups)
+constexpr int SWF_YR = 32;     // rows of an XTY entry at most
+constexpr int SWF_NCY = 36;    // columns (rows + Y columns) an XTY entry needs the statistics of, at most
 
-// thread = (column cl of the block's 16, fold fl): the fold's column sums from its s_diag partials,
-// the full-data sums over the folds through LDS, then the fold's mean / std
-template <typename T> __global__ __launch_bounds__(256) void sweep_stats_kernel(const FinArgs a, double *gstats) {
+// XTY entries: w Y columns (the power of two >= M, at most 32) x r rows
+struct SwfYShape { int w, r; };
+template <int PPR> __host__ __device__ inline SwfYShape swf_yshape(int M) {
+  int w = 1;
+  while (w < M && w < 32) w *= 2;
+  int r = swf4_ye<PPR>() / w;
+  if (r > SWF_YR) r = SWF_YR;
+  return {w, r};
+}
+static_assert(swf4_ye<SWF4_PPR>() / 32 + 32 <= SWF_NCY && SWF_YR + swf4_ye<SWF4_PPR>() / SWF_YR <= SWF_NCY, "SWF_NCY");
+
+// working blocks of a diagonal tile with nr block rows and nc block columns of C elements: block (r, c) holds
+// elements on or above the diagonal when c >= r * SWF_R / C (and that column exists whenever the row does)
+__host__ __device__ constexpr int swf_diag_blocks(int nr, int nc, int C) {
+  int n = 0;
+  for (int r = 0; r < nr; ++r) n += nc - r * SWF_R / C;
+  return n;
+}
+// the XTX entries of a K x K matrix with blocks of C columns, and entry x -> block (rb, cb); the map is arithmetic
+struct SwfList {
+  int nrb, ncb, pt, rpt, cpt, nc_l, dfull, dtot, n;
+  __host__ __device__ SwfList(int K, int C) {
+    nrb = (K + SWF_R - 1) / SWF_R; ncb = (K + C - 1) / C; pt = (K + TILE - 1) / TILE;
+    rpt = TILE / SWF_R; cpt = TILE / C;
+    nc_l = ncb - cpt * (pt - 1);
+    dfull = swf_diag_blocks(rpt, cpt, C);
+    dtot = (pt - 1) * dfull + swf_diag_blocks(nrb - rpt * (pt - 1), nc_l, C);
+    n = dtot;
+    for (int ti = 0; ti + 1 < pt; ++ti) n += rpt * (ncb - cpt * (ti + 1));
+  }
+  __device__ __forceinline__ void block(int x, int C, int &rb, int &cb) const {
+    if (x < dtot) {
+      const int t = x / dfull;          // (<= pt - 1: the last tile has at most dfull blocks)
+      int l = x - t * dfull, r = 0;
+      const int nc = (t == pt - 1) ? nc_l : cpt;
+      for (;; ++r) {
+        const int cnt = nc - r * SWF_R / C;
+        if (l < cnt) break;
+        l -= cnt;
+      }
+      rb = t * rpt + r; cb = t * cpt + r * SWF_R / C + l;
+    } else {
+      int y = x - dtot, ti = 0;
+      for (;; ++ti) {
+        const int cnt = rpt * (ncb - cpt * (ti + 1));
+        if (y < cnt) break;
+        y -= cnt;
+      }
+      const int cnt = ncb - cpt * (ti + 1);
+      rb = ti * rpt + y / cnt; cb = cpt * (ti + 1) + y % cnt;
+    }
+  }
+};
+
+// (an XTX entry's column sums and totals share their LDS with the transposition buffers, which are first written behind
+//  the barrier that follows the last read of the sums: in float64 the entry then needs exactly what the finish kernel
+//  without the statistics needed -- three workgroups per CU at 16 folds, not two)
+template <typename T, int PPR> constexpr size_t swf4_lds_bytes(int P) {
+  constexpr int VW = 16 / (int)sizeof(T), C = PPR * VW, SL = 32 + 2 * C + 1, NP = 16 * PPR;
+  const size_t sums = 2 * (size_t)P * (16 + C) * 8 + 3 * SWF_MAX * 8, tm = (size_t)SWF4_FG * 16 * (C + 1) * sizeof(T);
+  const size_t xtx = (size_t)P * NP * VW * 8 + (size_t)P * SL * 8 + (sums > tm ? sums : tm) + 16;
+  const size_t xty = (size_t)P * (swf4_ye<PPR>() + 1) * 8 + 4 * (size_t)P * SWF_NCY * 8 + 4 * SWF_MAX * 8;
+  return xtx > xty ? xtx : xty;
+}
+
+// The columns an entry needs the statistics of, n slots: slot j < na is X column xa + j, slot j >= na is column
+// b + j - na of X (b_is_x) or of Y
+struct SwfCols {
+  int n, na, xa, b;
+  bool b_is_x;
+  __device__ __forceinline__ void column(const Geom &g, int j, bool &isX, int &cc, bool &valid) const {
+    isX = j < na || b_is_x;
+    cc = j < na ? xa + j : b + (j - na);
+    valid = cc < (isX ? g.K : g.M);
+  }
+};
+
+// thread = (column slot j, fold fl): the fold's column sums from its s_diag partials in split order -> ss, qq [fl][j];
+// 3 P further threads sum every fold's sw, nz, neg -> tot.  The pairs are dealt from the LAST thread down: the last fold
+// groups are the ones with a fold less to load when the folds are no multiple of the groups (ten folds: 3, 3, 2, 2)
+template <typename T, int NT>
+__device__ __forceinline__ void swf_column_sums(const FinArgs &a, const SwfCols &c, double *ss, double *qq,
+                                                double (*tot)[SWF_MAX]) {
   const Geom &g = a.g;
-  const int K = g.K, M = g.M, P = a.n_seg;
-  const int tid = threadIdx.x, cl = tid & 15, fl = tid >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  const bool cvalid = c < K + M, fvalid = fl < P;
-  const bool isX = c < K;
-  const int cc = isX ? c : c - K;
-  const int s_src = isX ? cc : 2 * g.Kp + cc;
-  const int q_src = isX ? g.Kp + cc : 2 * g.Kp + g.Mp + cc;
-  __shared__ double ss[SWF_MAX][17], qq[SWF_MAX][17], tot[3][SWF_MAX];
-  const bool weighted = a.w != nullptr;
-  double sv = 0, qv = 0, tv = 0;
-  const long u0 = (long)fl * a.splits;
-  if (fvalid) {
-    const int t_src = (int)(2 * g.Kp + 2 * g.Mp) + (cl < 3 ? cl : 0);    // sw, nz, neg of the fold (cl 0..2)
+  const int P = a.n_seg;
+  const int np = c.n * P;
+  for (int q = NT - 1 - (int)threadIdx.x; q < np + 3 * P; q += NT) {
+    if (q >= np) {
+      // (the 3 P pairs behind the columns': sw, nz, neg of every fold -- a thread of their own, so that no thread
+      //  keeps a third set of partials in registers)
+      const int k = (q - np) / P, fl = (q - np) - k * P;
+      const int t_src = (int)(2 * g.Kp + 2 * g.Mp) + k;
+      const long u0 = (long)fl * a.splits;
+      double tv = 0;
+      for (int p0 = 0; p0 < a.s_diag; p0 += 8) {
+        const int cnt = a.s_diag - p0 < 8 ? a.s_diag - p0 : 8;
+        double t8[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) t8[i] = unit_stats<T>((char *)a.ws, g, u0 + p0 + (i < cnt ? i : 0))[t_src];
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          if (i < cnt) tv += t8[i];
+      }
+      tot[k][fl] = tv;
+      continue;
+    }
+    const int fl = q / c.n, j = q - fl * c.n;
+    bool isX, cvalid;
+    int cc;
+    c.column(g, j, isX, cc, cvalid);
+    const int s_src = isX ? cc : 2 * g.Kp + cc;
+    const int q_src = isX ? g.Kp + cc : 2 * g.Kp + g.Mp + cc;
+    const long u0 = (long)fl * a.splits;
+    double sv = 0, qv = 0;
     for (int p0 = 0; p0 < a.s_diag; p0 += 8) {
       const int cnt = a.s_diag - p0 < 8 ? a.s_diag - p0 : 8;
-      double s8[8], q8[8], t8[8];
+      double s8[8], q8[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const double *st = unit_stats<T>((char *)a.ws, g, u0 + p0 + (j < cnt ? j : 0));
-        s8[j] = cvalid ? st[s_src] : 0.0; q8[j] = cvalid ? st[q_src] : 0.0; t8[j] = st[t_src];
+      for (int i = 0; i < 8; ++i) {
+        const double *st = unit_stats<T>((char *)a.ws, g, u0 + p0 + (i < cnt ? i : 0));
+        s8[i] = cvalid ? st[s_src] : 0.0; q8[i] = cvalid ? st[q_src] : 0.0;
       }
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < cnt) { sv += s8[j]; qv += q8[j]; tv += t8[j]; }
+      for (int i = 0; i < 8; ++i)
+        if (i < cnt) { sv += s8[i]; qv += q8[i]; }
     }
-    ss[fl][cl] = sv; qq[fl][cl] = qv;
-    if (cl < 3) tot[cl][fl] = tv;
+    ss[q] = sv; qq[q] = qv;
   }
-  __syncthreads();
-  double gs = 0, gq = 0, gsw = 0, gnz = 0, gng = 0;
-  for (int f = 0; f < P; ++f) { gs += ss[f][cl]; gq += qq[f][cl]; gsw += tot[0][f]; gnz += tot[1][f]; gng += tot[2][f]; }
-  if (fl == 0 && cvalid) {
-    gstats[isX ? cc : 2 * K + cc] = gs;
-    gstats[isX ? K + cc : 2 * K + M + cc] = gq;
-  }
-  if (blockIdx.x == 0 && tid == 0) {
-    gstats[2 * K + 2 * M] = gsw; gstats[2 * K + 2 * M + 1] = gnz;
-    if (a.neg_flag) *a.neg_flag = (gng > 0) ? 1 : 0;
-  }
-  if (!fvalid || !a.fstats) return;
-  double swv, nzv;
-  if (weighted) { swv = tot[0][fl]; nzv = tot[1][fl]; }
-  else swv = nzv = (double)(a.offs[a.seg0 + fl + 1] - a.offs[a.seg0 + fl]);
-  const double swt = gsw - swv, nzt = gnz - nzv;
-  const double divisor = (nzt - a.ddof) * swt / nzt;
-  double *fs = a.fstats + (size_t)fl * fstat_len(K, M);
-  if (blockIdx.x == 0 && cl == 0) {
-    fs[2 * K + 2 * M] = swt;
-    if (a.out_fold) {
-      double *o = a.out_fold + 4 * (a.seg0 + fl);
-      o[0] = swt; o[1] = nzt; o[2] = swv; o[3] = nzv;
-    }
-  }
+}
+
+// after a barrier, the same thread: the full-data sums over the folds in fold order, then the fold's mean and
+// reciprocal std -> put(fl, j, mean, reciprocal std, sw of the training set).  own_a / own_b: this entry is the
+// designated writer of the slots j < na / j >= na; own_tot: of the totals
+template <typename T, int NT, typename Put>
+__device__ __forceinline__ void swf_column_stats(const FinArgs &a, const SwfCols &c, const double *ss, const double *qq,
+                                                 const double (*tot)[SWF_MAX], bool own_a, bool own_b, bool own_tot,
+                                                 double *gstats, Put put) {
+  const Geom &g = a.g;
+  const int K = g.K, M = g.M, P = a.n_seg;
   const bool cX = a.flags & CVM_CENTER_X, cY = a.flags & CVM_CENTER_Y;
   const bool sX = a.flags & CVM_SCALE_X, sY = a.flags & CVM_SCALE_Y;
   const bool rXTY = a.flags & CVM_RET_XTY;
   const bool want_muX = cX || sX || (rXTY && cY), want_sdX = sX;
   const bool want_muY = rXTY && (cX || cY || sY), want_sdY = rXTY && sY;
-  if (!cvalid || (isX ? !want_muX : !want_muY)) return;
-  fold_column_finish<T>(a, fl, isX, cc, sv, qv, gs, gq, swt, divisor, isX ? want_sdX : want_sdY, fs);
+  for (int q = NT - 1 - (int)threadIdx.x; q < c.n * P; q += NT) {
+    const int fl = q / c.n, j = q - fl * c.n;
+    bool isX, cvalid;
+    int cc;
+    c.column(g, j, isX, cc, cvalid);
+    double gs = 0, gq = 0, gsw = 0, gnz = 0, gng = 0;
+    for (int f = 0; f < P; ++f) {
+      gs += ss[f * c.n + j]; gq += qq[f * c.n + j];
+      gsw += tot[0][f]; gnz += tot[1][f]; gng += tot[2][f];
+    }
+    const bool own = j < c.na ? own_a : own_b;
+    if (own && fl == 0 && cvalid) {
+      gstats[isX ? cc : 2 * K + cc] = gs;
+      gstats[isX ? K + cc : 2 * K + M + cc] = gq;
+    }
+    if (own_tot && q == 0) {
+      gstats[2 * K + 2 * M] = gsw; gstats[2 * K + 2 * M + 1] = gnz;
+      if (a.neg_flag) *a.neg_flag = (gng > 0) ? 1 : 0;
+    }
+    double swv, nzv;
+    if (a.w != nullptr) { swv = tot[0][fl]; nzv = tot[1][fl]; }
+    else swv = nzv = (double)(a.offs[a.seg0 + fl + 1] - a.offs[a.seg0 + fl]);
+    const double swt = gsw - swv, nzt = gnz - nzv;
+    const double divisor = (nzt - a.ddof) * swt / nzt;
+    double *fs = a.fstats + (size_t)fl * fstat_len(K, M);
+    if (own_tot && j == 0) {
+      fs[2 * K + 2 * M] = swt;
+      if (a.out_fold) {
+        double *o = a.out_fold + 4 * (a.seg0 + fl);
+        o[0] = swt; o[1] = nzt; o[2] = swv; o[3] = nzv;
+      }
+    }
+    double mu = 0.0, isd = 1.0;
+    if (cvalid && (isX ? want_muX : want_muY)) {
+      const bool want_sd = isX ? want_sdX : want_sdY;
+      double sd;
+      column_mean_std(ss[q], qq[q], gs, gq, swt, divisor, want_sd, a.resolution, mu, sd);
+      isd = 1.0 / sd;
+      if (own) fold_column_store<T>(a, fl, isX, cc, mu, sd, want_sd, fs);
+    }
+    put(fl, j, mu, isd, swt);
+  }
 }
 
 // ----------------------------------------------------------------------------------
-// sweep_finish4_kernel (round 6): blocks of SWF_R rows x PPR 16-byte pieces over the upper triangle of the K x K matrices
-// (a block is inside one 128 x 128 tile of the partials), then ceil(K M / EPW) workgroups for XTY.  The folds' partial
-// loads are dealt over FOUR groups of threads: thread (piece, group g) loads the folds f = g, g + 4, ... only (2-3
-// dependent round trips at C3; round 2's 256-thread kernel walked its <= 16 folds one after the other -- ten round trips
-// per thread, barely more than one workgroup per CU (272 blocks): 25 us for 84 MB, 3.4 TB/s, latency-bound, profiles/r6/
-// pmc_derived.json), leaves each fold's update U_f in LDS as float64, and after one barrier every thread forms G = sum_f
-// U_f in fold order from LDS and group g finishes and stores the outputs o = g, g + 4, ... (o = 0: the full-data matrix;
-// o >= 1: fold o - 1), four matrices per barrier round through four transposition buffers: every finished matrix is
-// stored as rows a / columns b and, through the LDS transpose, as rows b / columns a; elements below the diagonal are
-// masked (the partials hold nothing there).  Needs 16-byte aligned rows (K * sizeof(T) % 16 == 0) and P <= SWF_MAX.
-// Dynamic LDS: P x 16 PPR pieces x 16 or 32 bytes + the statistics + the buffers (at SWF_MAX folds 50 KB float64, 86 KB float32).
+// sweep_finalize_kernel.  An XTX entry: the folds' partial loads are dealt over FOUR groups of threads: thread
+// (piece, group g) loads the folds f = g, g + 4, ... only (2-3 dependent round trips at C3; round 2's 256-thread kernel
+// walked its <= 16 folds one after the other -- ten round trips per thread, barely more than one workgroup per CU (272
+// blocks): 25 us for 84 MB, 3.4 TB/s, latency-bound, profiles/r6/pmc_derived.json), leaves each fold's update U_f in LDS
+// as float64, and after one barrier every thread forms G = sum_f U_f in fold order from LDS and group g finishes and
+// stores the outputs o = g, g + 4, ... (o = 0: the full-data matrix; o >= 1: fold o - 1), four matrices per barrier
+// round through four transposition buffers: every finished matrix is stored as rows a / columns b and, through the LDS
+// transpose, as rows b / columns a; elements below the diagonal are masked (the partials hold nothing there).  The
+// threads that hold a (column, fold) pair of the block's 16 + C columns sum that pair's partials and park the sums in LDS
+// BEFORE they request their tile partials -- a dependent round trip of their own, not an overlap (two where the pairs
+// and the totals outnumber the threads: float32 from 11 folds on, float64 from 15) --, and the sums become the statistics table behind the barrier that
+// ends the load phase.  An XTY entry deals its folds over the four groups in the same
+// way: thread = (element, group).  Needs 16-byte aligned rows (K * sizeof(T) % 16 == 0) and P <= SWF_MAX.
+// Dynamic LDS: P x 16 PPR pieces x 16 or 32 bytes + the statistics + the buffers (at SWF_MAX folds 49 KB float64, 89 KB float32).
 // ----------------------------------------------------------------------------------
-// PPR = 16-byte pieces per block row: 8 (16 rows x 128 bytes, 512 threads, 528 blocks at K = 512: two to four workgroups
-// per CU, so that one's loads overlap another's stores) rather than 16 (blocks of 16 rows x 256 bytes, 1024 threads, 272
-// blocks).
-constexpr int SWF4_FG = 4;
-constexpr int SWF4_PPR = 8;
-template <int PPR> constexpr int swf4_threads() { return 16 * PPR * SWF4_FG; }
-template <int PPR> constexpr int swf4_epw() { return swf4_threads<PPR>() / SWF_MAX; }      // XTY elements per workgroup
-template <typename T, int PPR> constexpr size_t swf4_lds_bytes(int P) {
-  constexpr int VW = 16 / (int)sizeof(T), C = PPR * VW, SL = 32 + 2 * C + 1, NP = 16 * PPR;
-  const size_t xtx = (size_t)P * NP * VW * 8 + (size_t)P * SL * 8 + (size_t)SWF4_FG * 16 * (C + 1) * sizeof(T) + 16;
-  const size_t xty = (size_t)SWF_MAX * (swf4_epw<PPR>() + 1) * 8;
-  return xtx > xty ? xtx : xty;
-}
-template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) void sweep_finish4_kernel(const FinArgs a, T *Gout, T *Hout) {
-  constexpr int SWF4_T = swf4_threads<PPR>(), SWF4_EPW = swf4_epw<PPR>(), NP = 16 * PPR;
-  static_assert(SWF_R == 16, "blocks of 16 rows x 256 bytes");
+// At least six waves per SIMD, i.e. THREE workgroups per CU (the kernel takes 71 registers): at C3 every entry is
+// resident at once (592 on 768 places).  Left to itself the compiler takes 94-100 registers (two workgroups per CU):
+// 25.2 us; eight waves (64 registers, 84 scalar registers spilling into them): 23.3; six: 22.4 (rocprofv3, same
+// box, profiles/sweep_finish/).
+constexpr int SWF_WPE = 6;
+template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG, SWF_WPE) void sweep_finalize_kernel(const FinArgs a, T *Gout, T *Hout, double *gstats) {
+  constexpr int SWF4_T = swf4_threads<PPR>(), SWF4_YE = swf4_ye<PPR>(), NP = 16 * PPR;
+  static_assert(SWF_R == 16, "blocks of 16 rows x PPR 16-byte pieces");
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   const Geom &g = a.g;
   const int K = g.K, M = g.M, P = a.n_seg;
@@ -1087,23 +1225,35 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
   constexpr int VW = 16 / (int)sizeof(T);
   constexpr int C = PPR * VW;                // block columns
   typedef T vld_t __attribute__((ext_vector_type(VW)));
-  const int nrb = (K + SWF_R - 1) / SWF_R, ncb = (K + C - 1) / C;
   const bool cX = a.flags & CVM_CENTER_X, cY = a.flags & CVM_CENTER_Y;
   const bool sX = a.flags & CVM_SCALE_X, sY = a.flags & CVM_SCALE_Y;
+  const SwfList list(K, C);
   const int x = blockIdx.x;
-  if (x >= nrb * ncb) {
-    // ---- XTY: thread = (element el of the workgroup's EPW, fold fl): the fold's update from its s_diag partials,
-    // H = their sum over the folds through LDS, then the fold's own result
+  if (x >= list.n) {
+    // ---- XTY: thread = (element el of the entry's r rows x w columns, group fg): the updates of the group's folds from
+    // their s_diag partials, H = their sum over the folds through LDS, then the group's folds' own results
+    // (never taken: the launch has XTY entries only with Y and M > 0, and cvm_sweep_all refuses M > 0 without Y and H --
+    //  so the Y columns' statistics, which these entries write, always have their writer)
     if (M == 0 || !Hout) return;
-    const int el = tid % SWF4_EPW, fl = tid / SWF4_EPW;
-    const int e = (x - nrb * ncb) * SWF4_EPW + el;
-    const bool evalid = e < K * M, fvalid = fl < P;
-    const int ga = evalid ? e / M : 0, m = evalid ? e - ga * M : 0;
+    const SwfYShape ys = swf_yshape<PPR>(M);
+    const int nyc = (M + ys.w - 1) / ys.w;
+    const int rg = (x - list.n) / nyc, yc = (x - list.n) - rg * nyc;
+    const int el = tid % SWF4_YE, fg = tid / SWF4_YE;
+    const int er = el / ys.w, ec = el - er * ys.w;
+    const int ga = rg * ys.r + er, m = yc * ys.w + ec;
+    const bool evalid = er < ys.r && ga < K && m < M;
     const size_t hoff = (g.tile_elems * sizeof(T) + 255) / 256 * 256;
-    double (*uh)[SWF4_EPW + 1] = reinterpret_cast<double (*)[SWF4_EPW + 1]>(dsm);     // (SWF_MAX x (EPW + 1) doubles)
-    double u = 0;
-    if (fvalid) {
-      const char *pf = a.ws + hoff + ((size_t)ga * g.Mp + m) * sizeof(T) + (size_t)fl * a.splits * g.unit_bytes;
+    // dynamic LDS: [P][YE + 1] updates | ss, qq, means, reciprocal stds [P][NCY] each | sw of the training sets | totals
+    double (*uh)[SWF4_YE + 1] = reinterpret_cast<double (*)[SWF4_YE + 1]>(dsm);
+    double *ss = reinterpret_cast<double *>(dsm) + (size_t)P * (SWF4_YE + 1), *qq = ss + (size_t)P * SWF_NCY;
+    double *mus = qq + (size_t)P * SWF_NCY, *isds = mus + (size_t)P * SWF_NCY, *swts = isds + (size_t)P * SWF_NCY;
+    double (*tot)[SWF_MAX] = reinterpret_cast<double (*)[SWF_MAX]>(swts + SWF_MAX);
+    const SwfCols cols = {ys.r + ys.w, ys.r, rg * ys.r, yc * ys.w, false};
+    swf_column_sums<T, SWF4_T>(a, cols, ss, qq, tot);
+    for (int f = fg; f < P; f += SWF4_FG) {
+      double u = 0;
+      const char *pf = a.ws + hoff + ((size_t)(evalid ? ga : 0) * g.Mp + (evalid ? m : 0)) * sizeof(T) +
+                       (size_t)f * a.splits * g.unit_bytes;
       for (int p0 = 0; p0 < a.s_diag; p0 += 8) {
         const int cnt = a.s_diag - p0 < 8 ? a.s_diag - p0 : 8;
         T t8[8];
@@ -1112,61 +1262,53 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
 #pragma unroll
         for (int j = 0; j < 8; ++j) if (j < cnt) u += (double)t8[j];
       }
-      uh[fl][el] = u;
+      uh[f][el] = u;
     }
     lds_barrier();
+    swf_column_stats<T, SWF4_T>(a, cols, ss, qq, tot, false, rg == 0, false, gstats,
+                                [&](int fl, int j, double mu, double isd, double swt) {
+                                  mus[fl * SWF_NCY + j] = mu; isds[fl * SWF_NCY + j] = isd;
+                                  if (j == 0) swts[fl] = swt;
+                                });
     double h = 0;
     for (int f = 0; f < P; ++f) h += uh[f][el];
     const T hT = (T)h;
-    if (!evalid) return;
-    if (fl == 0) Hout[(size_t)ga * M + m] = hT;
-    if (!a.out_XTY || !fvalid) return;
-    {
-      const double *fs = a.fstats + (size_t)fl * fstat_len(K, M);
-      const double swt = fs[2 * K + 2 * M];
-      double v = (double)hT - u;
-      if (cX || cY) v -= swt * (fs[ga] * fs[2 * K + m]);
-      if (sX && sY) v = v * (fs[K + ga] * fs[2 * K + M + m]);
-      else if (sX) v = v * fs[K + ga];
-      else if (sY) v = v * fs[2 * K + M + m];
-      ((T *)a.out_XTY)[((size_t)(a.seg0 + fl) * K + ga) * M + m] = (T)v;
+    if (evalid && fg == 0) Hout[(size_t)ga * M + m] = hT;
+    lds_barrier();
+    if (!evalid || !a.out_XTY) return;
+    for (int f = fg; f < P; f += SWF4_FG) {
+      const double *mf = mus + f * SWF_NCY, *sf = isds + f * SWF_NCY;
+      double v = (double)hT - uh[f][el];
+      if (cX || cY) v -= swts[f] * (mf[er] * mf[ys.r + ec]);
+      if (sX && sY) v = v * (sf[er] * sf[ys.r + ec]);
+      else if (sX) v = v * sf[er];
+      else if (sY) v = v * sf[ys.r + ec];
+      ((T *)a.out_XTY)[((size_t)(a.seg0 + f) * K + ga) * M + m] = (T)v;
     }
     return;
   }
-  const int rb = x / ncb, cb = x - rb * ncb;
+  int rb, cb;
+  list.block(x, C, rb, cb);
   const int a0 = rb * SWF_R, b0 = cb * C;
-  if (b0 + C - 1 < a0) return;               // the whole block is below the diagonal
   const int pid = tid % NP, fg = __builtin_amdgcn_readfirstlane(tid / NP);      // piece of the block, fold group
   const int lr = pid / PPR, lc = (pid % PPR) * VW;
   const int gr = a0 + lr, gc = b0 + lc;
   const int ti = a0 / TILE, tj = b0 / TILE;
   const int nsp = (ti == tj) ? a.s_diag : a.s_off;
-#ifdef CVM_SWF_CONTIG_PROBE
-  // (timing probe only, WRONG results: what the kernel would take if a block's pieces of a partial tile were 4 KB in a row)
-  const size_t off = (size_t)tile_id(ti, tj, g.P) * TILE * TILE +
-                     (size_t)(((a0 - ti * TILE) / SWF_R) * (TILE / C) + (b0 - tj * TILE) / C) * (SWF_R * C) + (size_t)lr * C + lc;
-#else
   const size_t off = (size_t)tile_id(ti, tj, g.P) * TILE * TILE + (size_t)(a0 - ti * TILE + lr) * TILE + (b0 - tj * TILE + lc);
-#endif
   const char *pp = a.ws + off * sizeof(T);
-  constexpr int SL = 32 + 2 * C + 1;
-  // dynamic LDS: [P][NP][VW] float64 updates | [P][SL] float64 statistics | [FG][16][C + 1] T transposition buffers
+  constexpr int SL = 32 + 2 * C + 1, NCX = 16 + C;
+  // dynamic LDS: [P][NP][VW] float64 updates | [P][SL] float64 statistics | { ss, qq [P][NCX], totals } in the same
+  // bytes as the [FG][16][C + 1] T transposition buffers: the sums are last read when the table is formed, the buffers
+  // first written behind the barrier after it
   double *Us = reinterpret_cast<double *>(dsm);
-  double (*stl)[SL] = reinterpret_cast<double (*)[SL]>(dsm + (size_t)P * NP * VW * 8);
-  T (*tm)[SWF_R][C + 1] = reinterpret_cast<T (*)[SWF_R][C + 1]>(dsm + (size_t)P * NP * VW * 8 + (size_t)P * SL * 8);
-  if (a.out_XTX) {
-    for (int q = tid; q < P * SL; q += SWF4_T) {
-      const int f = q / SL, i = q - f * SL;
-      const double *fs = a.fstats + (size_t)f * fstat_len(K, M);
-      double v;
-      if (i < 16) v = (cX && a0 + i < K) ? fs[a0 + i] : 0.0;
-      else if (i < 32) v = (sX && a0 + i - 16 < K) ? fs[K + a0 + i - 16] : 1.0;
-      else if (i < 32 + C) v = (cX && b0 + i - 32 < K) ? fs[b0 + i - 32] : 0.0;
-      else if (i < 32 + 2 * C) v = (sX && b0 + i - 32 - C < K) ? fs[K + b0 + i - 32 - C] : 1.0;
-      else v = fs[2 * K + 2 * M];
-      stl[f][i] = v;
-    }
-  }
+  double (*stl)[SL] = reinterpret_cast<double (*)[SL]>(Us + (size_t)P * NP * VW);
+  double *ss = Us + (size_t)P * NP * VW + (size_t)P * SL, *qq = ss + (size_t)P * NCX;
+  double (*tot)[SWF_MAX] = reinterpret_cast<double (*)[SWF_MAX]>(qq + (size_t)P * NCX);
+  T (*tm)[SWF_R][C + 1] = reinterpret_cast<T (*)[SWF_R][C + 1]>(ss);
+  // ---- the column sums of the block's 16 rows (as columns) and C columns, every fold
+  const SwfCols cols = {NCX, 16, a0, b0, true};
+  swf_column_sums<T, SWF4_T>(a, cols, ss, qq, tot);
   // ---- this group's folds: the update of this thread's piece, in split order (up to 8 partials in flight) -> LDS
   // (the NEXT fold of the group requested before the current one is added -- two folds' loads in flight -- was measured
   //  SLOWER, 22.7 -> 26.9 us, as in the 256-thread kernel of round 2, 25 -> 49 us: more loads in flight per thread do
@@ -1192,6 +1334,18 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
     for (int e = 0; e < VW; ++e) Us[((size_t)f * NP + pid) * VW + e] = u[e];
   }
   lds_barrier();
+  // ---- the statistics table of the block: per fold [0,16) means of its rows, [16,32) their reciprocal stds, [32,32+C)
+  // means of its columns, [32+C,32+2C) their reciprocal stds, then sw of the training set.  (Formed under the first
+  // partial loads instead, behind a barrier of its own inside the load loop: 22.7 against 22.4 us, and eight more
+  // registers held across it.)
+  swf_column_stats<T, SWF4_T>(a, cols, ss, qq, tot, cb == a0 / C, false, x == 0, gstats,
+                              [&](int fl, int j, double mu, double isd, double swt) {
+                                double *st = stl[fl];
+                                const int i = j < 16 ? j : 32 + (j - 16);
+                                st[i] = cX ? mu : 0.0;
+                                st[i + (j < 16 ? 16 : C)] = sX ? isd : 1.0;
+                                if (j == 0) st[32 + 2 * C] = swt;
+                              });
   // ---- G = sum of the folds' updates in fold order (every group forms it for itself: the same chain)
   double gsum[VW];
 #pragma unroll
@@ -1207,6 +1361,7 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
   T gT[VW];
 #pragma unroll
   for (int e = 0; e < VW; ++e) gT[e] = (T)gsum[e];
+  lds_barrier();
   // ---- outputs: o = 0 the full-data matrix, o >= 1 fold o - 1; group fg takes o = fg, fg + 4, ...: finished pieces are
   // stored as rows a / columns b and parked in the group's buffer; after one barrier the image is stored transposed
   const int mc = pid / (SWF_R / VW), mr = (pid - mc * (SWF_R / VW)) * VW;
@@ -1233,31 +1388,21 @@ template <typename T, int PPR> __global__ __launch_bounds__(16 * PPR * SWF4_FG) 
         out = (T *)a.out_XTX + (size_t)(a.seg0 + o - 1) * K * K;
       }
       T *dst = out + (size_t)gr * K + gc;
-#ifdef CVM_SWF_NO_DIRECT_PROBE
-      if (false) {
-#else
       if (all_ok) {
-#endif
         vld_t vv;
 #pragma unroll
         for (int e = 0; e < VW; ++e) vv[e] = vals[e];
         if (o) out_store(reinterpret_cast<vld_t *>(dst), vv); else *reinterpret_cast<vld_t *>(dst) = vv;
       } else {
-#ifndef CVM_SWF_NO_DIRECT_PROBE
 #pragma unroll
         for (int e = 0; e < VW; ++e) if (ok[e]) dst[e] = vals[e];
-#endif
       }
 #pragma unroll
       for (int e = 0; e < VW; ++e) tm[fg][lr][lc + e] = vals[e];
     }
     lds_barrier();
     const int orow = b0 + mc, ocol = a0 + mr;
-#ifdef CVM_SWF_NO_MIRROR_PROBE
-    if (o < n_out && orow < K && tm[fg][0][0] == (T)12345.678) {      // (timing probe: never true)
-#else
     if (o < n_out && orow < K) {
-#endif
       T *md = out + (size_t)orow * K + ocol;
       if (ocol + VW <= K && ocol + VW - 1 < orow) {
         vld_t vv;

@@ -1218,8 +1218,8 @@ int sweep_folds_impl(const int64_t *offsets, int64_t n_total, int64_t fold0, int
 }
 
 // cvm_sweep_all: cvm_sweep_fit and cvm_sweep_folds in one call.  With few folds (<= SWF_MAX) and
-// 16-byte aligned rows the finalize half is two launches that read every partial once
-// (sweep_stats_kernel, sweep_finish4_kernel); otherwise the two calls' own kernels.  Same bits.
+// 16-byte aligned rows the finalize half is one launch that reads every partial once
+// (sweep_finalize_kernel); otherwise the two calls' own kernels.  Same bits.
 template <typename T>
 int sweep_all_impl(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
                    const int64_t *host_offsets, int64_t n_folds, int64_t N, int K, int M, int dtype, unsigned flags,
@@ -1272,24 +1272,25 @@ int sweep_all_impl(const void *X, const void *Y, const void *w, const int64_t *i
   f.out_XTY = want_xty ? out_XTY : nullptr;
   f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
   f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
-  hipLaunchKernelGGL((sweep_stats_kernel<T>), dim3((unsigned)((K + M + 15) / 16)), dim3(256), 0, st, f, gstats);
-  // (round 6) the folds' partial loads dealt over four groups of threads -- 2-3 dependent round trips per thread instead
-  // of ten, the same sums; its LDS (the folds' updates of a block, float64) fits for every n_folds <= SWF_MAX
+  // one launch, one workgroup per entry of its list (finalize.hpp): the blocks of the upper triangle that hold
+  // elements, those of the diagonal tiles first, then the XTY rectangles; every workgroup forms the fold statistics
+  // it needs itself.  Its LDS (the folds' updates of a block, float64) fits for every n_folds <= SWF_MAX
   constexpr int PPR = SWF4_PPR;
-  static_assert(swf4_lds_bytes<T, PPR>(SWF_MAX) <= (size_t)150 * 1024, "sweep_finish4_kernel: LDS");
+  static_assert(swf4_lds_bytes<T, PPR>(SWF_MAX) <= (size_t)150 * 1024, "sweep_finalize_kernel: LDS");
   const size_t lds4 = swf4_lds_bytes<T, PPR>((int)n_folds);
   int dev = 0;
   HIP_OK(hipGetDevice(&dev));
   static std::atomic<unsigned long long> attr_done{0};   // one bit per device
   if (attr_needed(attr_done, dev)) {
-    HIP_OK(hipFuncSetAttribute((const void *)sweep_finish4_kernel<T, PPR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    HIP_OK(hipFuncSetAttribute((const void *)sweep_finalize_kernel<T, PPR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     attr_set(attr_done, dev);
   }
   constexpr int C = PPR * (16 / (int)sizeof(T));
-  const unsigned xb = (unsigned)(((K + SWF_R - 1) / SWF_R) * ((K + C - 1) / C));
-  const unsigned hb = (Y && M > 0) ? (unsigned)(((size_t)K * M + swf4_epw<PPR>() - 1) / swf4_epw<PPR>()) : 0u;
-  hipLaunchKernelGGL((sweep_finish4_kernel<T, PPR>), dim3(xb + hb), dim3(swf4_threads<PPR>()), lds4, st, f, (T *)G,
-                     (T *)((Y && M > 0) ? H : nullptr));
+  const unsigned xb = (unsigned)SwfList(K, C).n;
+  const SwfYShape ys = swf_yshape<PPR>(M);
+  const unsigned hb = (Y && M > 0) ? (unsigned)(((K + ys.r - 1) / ys.r) * ((M + ys.w - 1) / ys.w)) : 0u;
+  hipLaunchKernelGGL((sweep_finalize_kernel<T, PPR>), dim3(xb + hb), dim3(swf4_threads<PPR>()), lds4, st, f, (T *)G,
+                     (T *)((Y && M > 0) ? H : nullptr), gstats);
   HIP_OK(hipGetLastError());
   if (splits_out) *splits_out = (int64_t)p.s_off | ((int64_t)p.s_diag << 20);
   return CVM_OK;

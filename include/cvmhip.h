@@ -168,8 +168,8 @@ int cvm_sweep_folds(const int64_t *offsets, int64_t n_folds, int K, int M, int d
 
 /* cvm_sweep_fit followed by cvm_sweep_folds over all folds, as one call (same arguments, same
  * results to the bit, the partials stay in ws for cvm_sweep_fold_range).  With at most 16 folds
- * and 16-byte aligned rows the finalize half runs as two launches that read every partial once:
- * a fold's update stays in registers while the full-data matrix is formed as the sum of the
+ * and 16-byte aligned rows the finalize half runs as one launch that reads every partial once:
+ * a fold's update stays on chip while the full-data matrix is formed as the sum of the
  * folds' updates. */
 int cvm_sweep_all(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
                   const int64_t *host_offsets, int64_t n_folds, int64_t N, int K, int M, int dtype, unsigned flags,
