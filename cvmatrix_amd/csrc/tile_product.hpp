@@ -60,7 +60,11 @@ __device__ __forceinline__ double predict_rcp(double sd) {
   return fma(fma(-sd, r, 1.0), r, r);
 }
 struct ScorerRcp {
-  static __device__ __forceinline__ double lds(double sd) { return 1.0 / sd; }
+  // (the division alone would turn an infinite sd into the reciprocal 0 and the fold's sums into finite numbers
+  //  that ignore the column; NaN as on the other route and in predict_rcp.  sd - sd is +0 for a finite sd, which
+  //  keeps the division's bits -- 1 / sd is never -0 -- and NaN for an infinite or NaN one; no compare, no select:
+  //  a select cost pls_sse_kernel<double, 1, 2> three SGPRs, this form none in any variant.)
+  static __device__ __forceinline__ double lds(double sd) { return 1.0 / sd + (sd - sd); }
   static __device__ __forceinline__ double reg(double sd) {
     const double r = __builtin_amdgcn_rcp(sd);
     return fma(fma(-sd, r, 1.0), r, r);

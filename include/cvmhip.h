@@ -337,7 +337,24 @@ int cvm_pls_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M,
  * muX, sdX [n_folds][K], muY, sdY [n_folds][M] in `dtype`: the statistics outputs of cvm_fold_update
  * (NULL: no centring / no scaling).  B as cvm_pls_fit wrote it.  sse float64[n_folds][A][M], wsum
  * float64[n_folds].  MFMA in `dtype`, errors accumulated in float64 in a fixed order (no atomics).
- * RMSE of the cross-validation with a+1 components: sqrt(sum_f sse[f][a][m] / sum_f wsum[f]). */
+ * RMSE of the cross-validation with a+1 components: sqrt(sum_f sse[f][a][m] / sum_f wsum[f]).
+ * Limits: at most 65535 folds per call (one more: CVM_EINVAL, cvm_last_error names the limit; cut a longer
+ * batch into several calls); max_fold_rows is the longest fold or any upper bound of it.  ws_bytes below
+ * cvm_pls_sse_workspace_bytes: CVM_EWORKSPACE.  A refused call writes nothing; n_folds == 0 launches nothing.
+ * An empty fold, and a fold whose weights are all zero, has sse exactly 0 and wsum exactly 0; without
+ * weights wsum[f] is the fold's row count exactly.  A row may lie in several folds, or several times in one.
+ * Bits: sse[f][a][m] depends on the fold's rows (their x, y, w and their order in idx), the fold's statistics,
+ * its column B[f][a][:, m] and on where the plan keeps the fold's statistics (cvm_cv_predict_plan, info[7]) --
+ * not on the other folds or the fold's place in the batch, the other columns of B, max_fold_rows, the
+ * alignment of the arrays, what the workspace held, or the stream; the same call again gives the same bits.
+ * The two places of the statistics form 1 / sdX differently (a division; the reciprocal instruction with one
+ * Newton step, within a unit of it) and may differ in the last places: so may two calls whose K, M, A or
+ * alignment lead to different info[7].
+ * Non-finite input stays where it belongs and never becomes a finite number: an sdX[f][k] that is 0, infinite
+ * or NaN, or a muX[f][k] that is infinite or NaN, makes every sse[f][a][m] of that fold non-finite on both
+ * routes; a NaN in the column B[f][a][:, m] makes that one sum NaN; a NaN in y_im makes sse[f][:, m] NaN (with
+ * the row's weight 0 too: 0 * NaN is NaN); a NaN in a row of X makes the sums of the folds that hold the row
+ * NaN.  Every other sum keeps the bits it has when the input is clean. */
 size_t cvm_pls_sse_workspace_bytes(int64_t n_folds, int64_t max_fold_rows, int M, int A);
 int cvm_pls_validation_sse(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
                            int64_t n_folds, int64_t max_fold_rows, int K, int M, int A, int dtype, const void *muX,
