@@ -11,9 +11,15 @@
 //   waves 0-3  COMPUTE, one per SIMD.  They never touch global memory inside the loop, so no
 //              vector-memory instruction ever blocks their issue (a 1 KiB load costs its
 //              wave 200-450 cycles of issue on a busy CU: tools/dma_issue.hip).
-//              Off-diagonal tile (wgram4_body): wave (wr,wc) owns the 64x64 block (wr,wc) of
-//              the 128x128 tile: 4x4 MFMA tiles, 16 accumulators (128 VGPRs), 16 MFMAs per 8
-//              LDS fragment reads.
+//              Off-diagonal tile (wgram4_body): 16 accumulators (128 VGPRs), 16 MFMAs per k-step.
+//              Two-stage / sweep routes: wave w owns the 32x128 block of rows 32 w .. 32 w + 31
+//              (2 x 8 MFMA tiles, 2 weighting multiplies).  float64 reads its fragments in PAIRS:
+//              a lane takes columns 2 lc, 2 lc + 1 of a 32-column group by one ds_read_b128, the
+//              operands of two MFMA tiles, 1 + 1 + 4 LDS reads per k-step instead of 11, and
+//              stores two adjacent columns of a partial by one 16-byte store, 32 per item
+//              instead of 64 (see "The pair map" in wgram4_body); float32 keeps the 11 reads.
+//              Fused route: wave (wr,wc) owns the 64x64 block (wr,wc) of the 128x128 tile:
+//              4x4 MFMA tiles, 8 LDS fragment reads per k-step.
 //              Diagonal tile, first Y chunk (wgram4_diag_body): the upper triangle of the
 //              tile's 8x8 grid of MFMA tiles shared out evenly, 9 tiles + the XTY tiles and
 //              the column sums of two row-tiles per wave: 11 MFMAs per k-step.
@@ -40,7 +46,7 @@ template <typename T> __device__ __forceinline__ void partial_store(T *p, T v) {
 // tools/f32_loop_probe.hip: a vector instruction inside the MFMA stream costs the matrix pipe ~12 cycles in float32
 // (the float32 MFMA runs on the vector unit's own multipliers: the two are one resource), the 16 weighting
 // multiplies of a stage 8 % of the loop; with 8 of them 0.862 -> 0.890 of the peak in the probe.  Both element types
-// take 32 x 128 (profiles/r6/wide_blocks_ab.txt).
+// take 32 x 128 (profiles/r6/wide_blocks_ab.txt).  float64 fetches that block's fragments in pairs (profiles/gram_pairs).
 constexpr int NBUF4 = 4;        // LDS stage buffers
 constexpr size_t LDS4_BYTES = (size_t)NBUF4 * BUF_ELEMS * 8;   // float64; float32 uses half of it
 template <typename T> constexpr size_t lds4_bytes() { return (size_t)NBUF4 * BUF_ELEMS * sizeof(T); }
@@ -558,7 +564,41 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
       }
     }
   };
-  if (MFM || ROLE != 0) {
+  // The pair map (float64, the WIDE wave).  A lane takes the adjacent columns 2 lc, 2 lc + 1 of a 32-column group by
+  // ONE 16-byte LDS read: the operands of two MFMA tiles, the group's even and its odd columns.  Per k-step the
+  // weight, one A piece (panel columns 32 w + 2 lc, + 1: a_e, a_o) and four B pieces (32 g + 2 lc, + 1: b_ge, b_go)
+  // -- 6 reads instead of 11 for the same bytes.  af[][p] = a_p, bf[][2 g + q] = b_gq, so the MFMA sequence below
+  // is the one it was and accumulator acc[8 p + 2 g + q], register reg, holds
+  //     row 32 w + 2 drow(lane, reg) + p,  column 32 g + 2 lc + q
+  // of the tile.  Every element is still the chain of (w x_a) x_b over the same rows in the same order, whichever
+  // lane and register carries it: the same bits.  Every piece is 16-byte aligned (pitch 1152 B, panel 18 432 B,
+  // buffer 36 992 B), and the image the loaders leave in LDS -- clamped and zero-line columns included -- is
+  // read exactly as far as before.
+  // Addresses: the three per-lane LDS addresses (weight, A piece, B piece) of ONE ring buffer live in registers,
+  // everything else is an immediate.  They move to the next buffer behind three MFMAs of the third k-step (its
+  // reads are out by then); the fourth k-step reads the next buffer's first row group and the next stage goes
+  // on from there.  Inline asm pins them there: left to itself the compiler forms the addresses in one clump at
+  // the head of the stage and carries them over the back edge by three moves.
+  constexpr bool PAIRS = WIDE && sizeof(T) == 8;
+  typedef T pair_t __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(3))) char *ldsp_t;
+  const unsigned lds0p = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char *)smem_raw);
+  const unsigned oW = lds0p + (unsigned)sizeof(T) * (unsigned)(2 * PANEL_ELEMS + lk);
+  const unsigned oA = lds0p + (unsigned)sizeof(T) * (unsigned)(32 * wave + lk * PITCH + 2 * lc);
+  const unsigned oB = lds0p + (unsigned)sizeof(T) * (unsigned)(PANEL_ELEMS + lk * PITCH + 2 * lc);
+  ldsp_t cW = (ldsp_t)(uintptr_t)oW, cA = (ldsp_t)(uintptr_t)oA, cB = (ldsp_t)(uintptr_t)oB;
+  constexpr int RG = 4 * PITCH * (int)sizeof(T);      // bytes from one k-step's row group to the next
+  if constexpr (PAIRS) {
+    wv[0] = *reinterpret_cast<const __attribute__((address_space(3))) T *>(cW);
+    const pair_t ta = *reinterpret_cast<const __attribute__((address_space(3))) pair_t *>(cA);
+    af[0][0] = ta[0]; af[0][1] = ta[1];
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      const pair_t tb = *reinterpret_cast<const __attribute__((address_space(3))) pair_t *>(cB + 256 * gq);
+      bf[0][2 * gq] = tb[0]; bf[0][2 * gq + 1] = tb[1];
+    }
+    prepare(0);
+  } else if (MFM || ROLE != 0) {
     read_frags(smem, 0, 0);
     prepare(0);
   }
@@ -591,10 +631,26 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
         const int c = ks & 1;
         const T *rb = ks < 3 ? buf : nbuf;
         const int r = 4 * (ks < 3 ? ks + 1 : 0) + lk;
+        const unsigned nb_bytes = (unsigned)(((s + 1) % NBUF4) * BUF_ELEMS) * (unsigned)sizeof(T);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           acc[i] = MF<T>::mfma(af[c][i / NB], bf[c][i % NB], acc[i]);
-          if (WIDE) {
+          if constexpr (PAIRS) {
+            // the weight, the A piece it multiplies, the four B pieces; the two multiplies where they were
+            const int rs = ks < 3 ? ks + 1 : 0;
+            if (i == 0) wv[c ^ 1] = *reinterpret_cast<const __attribute__((address_space(3))) T *>(cW + 4 * (int)sizeof(T) * rs);
+            else if (i == 1) {
+              const pair_t ta = *reinterpret_cast<const __attribute__((address_space(3))) pair_t *>(cA + RG * rs);
+              af[c ^ 1][0] = ta[0]; af[c ^ 1][1] = ta[1];
+            } else if (i < 6) {
+              const pair_t tb = *reinterpret_cast<const __attribute__((address_space(3))) pair_t *>(cB + RG * rs + 256 * (i - 2));
+              bf[c ^ 1][2 * (i - 2)] = tb[0]; bf[c ^ 1][2 * (i - 2) + 1] = tb[1];
+            } else if (ks == 2 && i < 9) {
+              unsigned x;
+              asm volatile("v_add_u32 %0, %1, %2" : "=v"(x) : "s"(nb_bytes), "v"(i == 6 ? oW : i == 7 ? oA : oB));
+              if (i == 6) cW = (ldsp_t)(uintptr_t)x; else if (i == 7) cA = (ldsp_t)(uintptr_t)x; else cB = (ldsp_t)(uintptr_t)x;
+            } else if (WEIGHTED && i >= 13 && i < 15) af[c ^ 1][i - 13] *= wv[c ^ 1];
+          } else if (WIDE) {
             // the weight first, then the two A-side fragments it multiplies, then the eight of the B side
             if (i == 0) wv[c ^ 1] = rb[2 * PANEL_ELEMS + r];
             else if (i < 3) af[c ^ 1][i - 1] = rb[a_off + r * PITCH + 16 * (i - 1)];
@@ -813,6 +869,21 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
   } else if (do_g) {
     T *tp = unit_tiles<T>(a.ws, g, u) + (size_t)it * TILE * TILE;
     constexpr int SA = (HW || !MFM) ? 4 : NA, SB = (HW || !MFM) ? 4 : NB;      // (the block's MFMA tiles: 4 x 4, or 2 x 8)
+    if constexpr (PAIRS) {
+      // the pair map: a lane holds two adjacent columns of every row it holds: 32 sixteen-byte stores instead of 64
+      // eight-byte ones, to the same places (a tile row is 1 KiB, a pair starts at an even column)
+      typedef T pair8_t __attribute__((ext_vector_type(2), aligned(8)));
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int gq = 0; gq < 4; ++gq)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            pair8_t v;
+            v[0] = acc[8 * m + 2 * gq][r]; v[1] = acc[8 * m + 2 * gq + 1][r];
+            *reinterpret_cast<pair8_t *>(&tp[(a_col + 2 * MF<T>::drow(lane, r) + m) * TILE + 32 * gq + 2 * lc]) = v;
+          }
+    } else {
 #pragma unroll
     for (int m = 0; m < SA; ++m)
 #pragma unroll
@@ -820,6 +891,7 @@ __device__ __noinline__ ROLE_ATTR void wgram4_body(kargs_ptr<T> kargs, int xcd_q
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           partial_store(&tp[(a_col + 16 * m + MF<T>::drow(lane, r)) * TILE + b_col + 16 * n + lc], acc[m * SB + n][r]);
+    }
   }
 #ifdef CVM_STAMPS
   {

@@ -18,6 +18,9 @@
 //          wgram4_kernel does since round 2)
 //   14  as 12 in a function the compiler treats as an AccVGPR user: it then puts the accumulators
 //       into AccVGPRs itself -- 50.6 TFLOP/s: not the way on gfx950
+//   15/16  12 with the kernel's wide 32 x 128 block (2 A-side + 8 B-side fragments, 2 multiplies): the fragments
+//          in pairs by ds_read_b128 (1 + 1 + 4 reads per k-step) / today's 11 eight-byte reads -- the twins
+//          that profiles/gram_pairs/probe.txt compares
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/mfma_mix.hip -o tools/mfma_mix
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -167,6 +170,77 @@ template <int V> __global__ __launch_bounds__(512, 2) void kern(const double* in
         }
       }
       if (V == 12 || V == 14) __syncthreads();
+    }
+  } else if (V == 15 || V == 16) {
+    // variant 12 with the wide 32 x 128 block of today's kernel (wave w: rows 32 w .. 32 w + 31 of the tile, all of
+    // its columns: 2 A-side and 8 B-side fragments, 2 multiplies), the weight read first.
+    //   V == 16: today's 11 eight-byte reads per k-step
+    //   V == 15: the fragments in pairs -- a lane takes columns 2 lc, 2 lc + 1 of a 32-column group by one
+    //            ds_read_b128: 1 weight read, 1 A read, 4 B reads per k-step; one address per ring buffer and
+    //            operand kind, formed behind MFMAs of the third k-step
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    typedef const __attribute__((address_space(3))) char* ldsp;
+    double wa[2][2], wb[2][8], ww[2];
+    const int a1 = 32 * wave + lc, b1 = PANEL + lc;
+    const unsigned lds0 = (unsigned)(uintptr_t)(ldsp)(const __attribute__((address_space(3))) double*)smem;
+    const unsigned oA = lds0 + 8u * (32 * wave + lk * PITCH + 2 * lc), oB = lds0 + 8u * (PANEL + lk * PITCH + 2 * lc);
+    const unsigned oW = lds0 + 8u * (2 * PANEL + lk);
+    ldsp cA = (ldsp)(uintptr_t)oA, cB = (ldsp)(uintptr_t)oB, cW = (ldsp)(uintptr_t)oW;
+    if (V == 16) {
+      wa[0][0] = smem[a1 + lk * PITCH]; wa[0][1] = smem[a1 + lk * PITCH + 16];
+#pragma unroll
+      for (int n = 0; n < 8; ++n) wb[0][n] = smem[b1 + lk * PITCH + 16 * n];
+    } else {
+      const d2 t = *(const __attribute__((address_space(3))) d2*)cA;
+      wa[0][0] = t[0]; wa[0][1] = t[1];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const d2 u = *(const __attribute__((address_space(3))) d2*)(cB + 256 * g);
+        wb[0][2 * g] = u[0]; wb[0][2 * g + 1] = u[1];
+      }
+    }
+    ww[0] = smem[2 * PANEL + lk];
+    wa[0][0] *= ww[0]; wa[0][1] *= ww[0];
+#pragma unroll 1
+    for (int s = 0; s < stages; ++s) {
+      const double* buf = smem + (s & 3) * BUF;
+      const double* nbuf = smem + ((s + 1) & 3) * BUF;
+      const unsigned nb = (unsigned)(((s + 1) & 3) * BUF) * 8u;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int c = ks & 1;
+        const double* rb = ks < 3 ? buf : nbuf;
+        const int rs = ks < 3 ? ks + 1 : 0;
+        const int r = 4 * rs + lk;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[c][i >> 3], wb[c][i & 7], acc[i], 0, 0, 0);
+          if (V == 16) {
+            if (i == 0) ww[c ^ 1] = rb[2 * PANEL + r];
+            else if (i < 3) wa[c ^ 1][i - 1] = rb[a1 + r * PITCH + 16 * (i - 1)];
+            else if (i < 11) wb[c ^ 1][i - 3] = rb[b1 + r * PITCH + 16 * (i - 3)];
+            else if (i >= 13 && i < 15) wa[c ^ 1][i - 13] *= ww[c ^ 1];
+          } else {
+            if (i == 0) ww[c ^ 1] = *(const __attribute__((address_space(3))) double*)(cW + 32 * rs);
+            else if (i == 1) {
+              const d2 t = *(const __attribute__((address_space(3))) d2*)(cA + 4 * PITCH * 8 * rs);
+              wa[c ^ 1][0] = t[0]; wa[c ^ 1][1] = t[1];
+            } else if (i < 6) {
+              const d2 t = *(const __attribute__((address_space(3))) d2*)(cB + 4 * PITCH * 8 * rs + 256 * (i - 2));
+              wb[c ^ 1][2 * (i - 2)] = t[0]; wb[c ^ 1][2 * (i - 2) + 1] = t[1];
+            } else if (ks == 2 && i >= 6 && i < 9) {
+              // the next ring buffer: its row group 0 is read in the fourth k-step, the others in the next stage
+              // (asm: the compiler would form the three addresses in one clump at the head of the stage and
+              //  carry them to the next one by three moves)
+              unsigned x;
+              asm volatile("v_add_u32 %0, %1, %2" : "=v"(x) : "s"(nb), "v"(i == 6 ? oW : i == 7 ? oA : oB));
+              if (i == 6) cW = (ldsp)(uintptr_t)x; else if (i == 7) cA = (ldsp)(uintptr_t)x; else cB = (ldsp)(uintptr_t)x;
+            } else if (i >= 13 && i < 15) wa[c ^ 1][i - 13] *= ww[c ^ 1];
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      __syncthreads();
     }
   } else if (V == 4) {
     for (int s = 0; s < stages * 8; ++s) {
@@ -349,6 +423,10 @@ int main() {
   run<13>(din, dout, "one read / multiply behind each MFMA, order pinned, no barrier");
   run<14>(din, dout, "the same + barrier, function marked as an AccVGPR user");
   run<6>(din, dout, "as the barrier line, fragments by ds_read_b128");
+  run<16>(din, dout, "wide 32x128 block, pinned, + barrier: 11 b64 reads");
+  run<15>(din, dout, "wide 32x128 block, pinned, + barrier: 1 + 5 reads (b128 pairs)");
+  run<16>(din, dout, "wide 32x128 block, pinned, + barrier: 11 b64 reads");
+  run<15>(din, dout, "wide 32x128 block, pinned, + barrier: 1 + 5 reads (b128 pairs)");
   run<7>(din, dout, "diagonal tile wave 0: 11 MFMAs, 10 b64 reads per k-step", 44.0);
   run<8>(din, dout, "diagonal tile wave 0: 11 MFMAs, 6 reads (b128)", 44.0);
   run8<0>(din, dout, "8 waves x 64x32 (2 per SIMD): reads + weighting + barrier");
