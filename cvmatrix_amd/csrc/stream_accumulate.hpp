@@ -13,6 +13,9 @@
 // off-diagonal tiles, s_diag for diagonal tiles, XTY panels and statistics) -- apply_kernel's "segment sum" --
 // and that sum is added to the accumulated element.  A stream of ONE chunk leaves 0 + U_f: the bits of
 // cvm_sweep_fit's fold updates.  A fold without rows in the chunk is skipped: its scratch slots are never read.
+// Nor are the strictly lower 16 x 16 blocks of a diagonal tile, which the Gram launch does not write (the finalize
+// kernels mirror the upper ones): the scratch is whatever the allocator hands out, and what it held there -- a NaN
+// of an earlier stream, say -- stays out of the accumulator, whose elements there stay zero.
 // No atomics, no workgroup waits for another.
 //
 // Traffic per chunk: every chunk partial read once + the accumulator units of the folds present read and
@@ -24,6 +27,7 @@ constexpr int STREAM_THREADS = 256;
 constexpr int STREAM_UNR = 4;                                   // 16-byte accumulator pieces per thread
 constexpr int STREAM_BLOCK_ELEMS = STREAM_THREADS * STREAM_UNR * 2;   // float64 elements per workgroup (2048)
 static_assert((TILE * TILE) % STREAM_BLOCK_ELEMS == 0, "a workgroup of stream_accumulate_kernel stays inside one tile");
+static_assert(STREAM_BLOCK_ELEMS == 16 * TILE, "a workgroup of stream_accumulate_kernel is one row of 16 x 16 blocks of a tile");
 
 // the host header of a stream (int64[CVM_STREAM_STATE_LEN], filled by cvm_stream_reset)
 constexpr int64_t STREAM_MAGIC = 0x43564d5354524d31ll;         // "CVMSTRM1"
@@ -55,8 +59,12 @@ inline void stream_blocks(StreamArgs &a) {
 
 // One workgroup: STREAM_BLOCK_ELEMS consecutive elements of one region (tiles | XTY panels | statistics) of
 // one fold's unit.  S: the element type of the region in the chunk's partials (T, or double for statistics).
+// `skip_cols`: the leading columns of every 128-element row of the run that no Gram launch writes and nothing reads
+// (a diagonal tile's strictly lower 16 x 16 blocks): left out, their accumulator elements stay as reset left them.
+// `n_written` (odd): the run's last element, n_elems - 1, is one no Gram launch writes; it is not added either.
 template <typename S>
-__device__ __forceinline__ void stream_add_run(const char *src, size_t slot_bytes, int nsp, double *dst, size_t e0, size_t n_elems) {
+__device__ __forceinline__ void stream_add_run(const char *src, size_t slot_bytes, int nsp, double *dst, size_t e0, size_t n_elems,
+                                               int skip_cols = 0, size_t n_written = ~(size_t)0) {
   typedef S vs_t __attribute__((ext_vector_type(2)));
   typedef double vd_t __attribute__((ext_vector_type(2)));
   size_t e[STREAM_UNR];
@@ -64,6 +72,7 @@ __device__ __forceinline__ void stream_add_run(const char *src, size_t slot_byte
 #pragma unroll
   for (int j = 0; j < STREAM_UNR; ++j) {
     e[j] = e0 + 2 * ((size_t)j * STREAM_THREADS + threadIdx.x);
+    if ((int)(e[j] % TILE) < skip_cols) e[j] = n_elems;          // (past the end: every guard below leaves it out)
     us[j] = (vd_t){0.0, 0.0};
     if (e[j] < n_elems) acc[j] = *reinterpret_cast<const vd_t *>(dst + e[j]);
   }
@@ -75,7 +84,7 @@ __device__ __forceinline__ void stream_add_run(const char *src, size_t slot_byte
       if (e[j] < n_elems) v[j] = *reinterpret_cast<const vs_t *>(p + e[j]);
 #pragma unroll
     for (int j = 0; j < STREAM_UNR; ++j)
-      if (e[j] < n_elems) { us[j][0] += (double)v[j][0]; us[j][1] += (double)v[j][1]; }
+      if (e[j] < n_elems) { us[j][0] += (double)v[j][0]; if (e[j] + 1 < n_written) us[j][1] += (double)v[j][1]; }
   }
 #pragma unroll
   for (int j = 0; j < STREAM_UNR; ++j)
@@ -97,16 +106,21 @@ template <typename T> __global__ __launch_bounds__(STREAM_THREADS) void stream_a
     const size_t e0 = (size_t)b * STREAM_BLOCK_ELEMS;
     int ti, tj;
     decode_tile((int)(e0 / (TILE * TILE)), gp.P, ti, tj);
-    stream_add_run<T>(src, gp.unit_bytes, ti == tj ? a.s_diag : a.s_off, (double *)dst, e0, ga.tile_elems);
+    // a workgroup = the 16 rows of one row of 16 x 16 blocks: on a diagonal tile the blocks left of the diagonal one
+    // are never written by the Gram launch (wgram4_diag_body stores the upper triangle of the 8 x 8 grid; the
+    // finalize kernels mirror it) -- adding them would carry whatever the scratch held into the accumulator
+    const int skip = ti == tj ? (int)(e0 % (TILE * TILE) / STREAM_BLOCK_ELEMS) * 16 : 0;
+    stream_add_run<T>(src, gp.unit_bytes, ti == tj ? a.s_diag : a.s_off, (double *)dst, e0, ga.tile_elems, skip);
   } else if ((b -= a.nb_t) < a.nb_h) {
     stream_add_run<T>(src + up256(gp.tile_elems * sizeof(T)), gp.unit_bytes, a.s_diag,
                       (double *)(dst + up256(ga.tile_elems * 8)), (size_t)b * STREAM_BLOCK_ELEMS, ga.h_elems);
   } else {
     b -= a.nb_h;
+    // (the statistics end in sw, nz, the count of negative weights and one spare word that nothing writes)
     stream_add_run<double>(src + up256(gp.tile_elems * sizeof(T)) + up256(gp.h_elems * sizeof(T)),
                            gp.unit_bytes, a.s_diag,
                            (double *)(dst + up256(ga.tile_elems * 8) + up256(ga.h_elems * 8)),
-                           (size_t)b * STREAM_BLOCK_ELEMS, ga.stat_len);
+                           (size_t)b * STREAM_BLOCK_ELEMS, ga.stat_len, 0, ga.stat_len - 1);
   }
 }
 
@@ -164,9 +178,10 @@ template <typename KERNEL> int stream_launch_folds(KERNEL kernel, StreamArgs a, 
 // bytes stream_accumulate_kernel moves for one chunk (the model the measurements are held against): the
 // partials of the folds present read once, their accumulator units read and written once
 inline size_t stream_add_traffic(const Geom &gp, const Geom &ga, int s_off, int s_diag, int64_t folds_present, int esize) {
-  const size_t off_tiles = (size_t)(gp.nTiles - gp.P) * TILE * TILE, diag_tiles = (size_t)gp.P * TILE * TILE;
+  // (a diagonal tile: the 36 of its 64 blocks of 16 x 16 on and above the diagonal)
+  const size_t off_tiles = (size_t)(gp.nTiles - gp.P) * TILE * TILE, diag_tiles = (size_t)gp.P * 36 * 256;
   const size_t partial = (off_tiles * s_off + (diag_tiles + gp.h_elems) * s_diag) * esize + gp.stat_len * 8 * s_diag;
-  const size_t unit = (ga.tile_elems + ga.h_elems + ga.stat_len) * 8;
+  const size_t unit = (off_tiles + diag_tiles + ga.h_elems + ga.stat_len) * 8;
   return (size_t)folds_present * (partial + 2 * unit);
 }
 

@@ -451,6 +451,11 @@ def ladder_columns(route):
     looks at a fixed sample of the columns -- the tile edges and seeded random ones, as many as that budget
     allows -- and measures error and yardstick on the same entries."""
     dtype, N, K, M, folds, style, rows = route_geometry(LADDER_ROUTES[route][0])
+    return sample_columns(N, K)
+
+
+def sample_columns(N, K):
+    """The column sample of ``ladder_columns`` for a problem of N rows and K columns (None: all columns)."""
     n = int(np.sqrt(2e7 / N))
     if n >= K:
         return None
