@@ -41,6 +41,7 @@ namespace {
 #include "small_folds.hpp"
 #include "resident.hpp"
 #include "mid_tile.hpp"
+#include "fold_plan.hpp"
 #include "host.hpp"
 #include "fold_unions.hpp"
 #include "stream_accumulate.hpp"
@@ -78,8 +79,8 @@ const char *cvm_last_error(void) { return g_err; }
 size_t cvm_gstats_len(int K, int M) { return 2 * (size_t)K + 2 * (size_t)M + 2; }
 
 size_t cvm_fit_workspace_bytes(int64_t N, int K, int M, int dtype) {
-  const Geom g = make_geom(K, M, dtype == CVM_F64 ? 8 : 4, 0);
-  return (size_t)plan_stride(1, N, g, dtype == CVM_F64 ? 8 : 4) * g.unit_bytes + QUEUE_RESERVE;
+  const Geom g = make_geom(K, M, esize_of(dtype), 0);
+  return (size_t)plan_stride(1, N, g, esize_of(dtype)) * g.unit_bytes + QUEUE_RESERVE;
 }
 
 int cvm_gram_fit(const void *X, const void *Y, const void *w, int64_t N, int K, int M, int dtype,
@@ -88,13 +89,9 @@ int cvm_gram_fit(const void *X, const void *Y, const void *w, int64_t N, int K, 
   if (!X || !G || !gstats || !ws) return fail(CVM_EINVAL, "cvm_gram_fit: null pointer%s");
   if (N < 0 || K <= 0 || M < 0 || (M > 0 && (!Y || !H)) || (M == 0 && Y))
     return fail(CVM_EINVAL, "cvm_gram_fit: bad shape%s");
-  if (dtype == CVM_F64)
-    return gram_fit_impl<double>(X, Y, w, N, K, M, dtype, G, H, gstats, neg_flag, ws, ws_bytes,
-                                 (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return gram_fit_impl<float>(X, Y, w, N, K, M, dtype, G, H, gstats, neg_flag, ws, ws_bytes,
-                                (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_gram_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_gram_fit", [&](auto t) {
+    return gram_fit_impl<decltype(t)>(X, Y, w, N, K, M, dtype, G, H, gstats, neg_flag, ws, ws_bytes, (hipStream_t)stream);
+  });
 }
 
 size_t cvm_fold_workspace_bytes(int64_t n_folds, int64_t n_idx, int64_t max_fold_rows, int K, int M,
@@ -102,15 +99,14 @@ size_t cvm_fold_workspace_bytes(int64_t n_folds, int64_t n_idx, int64_t max_fold
   (void)n_idx;
   if (max_fold_rows <= SMALL_ROWS) {   // direct path: only the per-fold statistics live in ws
     const int64_t nb = n_folds < 32768 ? (n_folds > 0 ? n_folds : 1) : 32768;
-    const size_t small = (size_t)nb * small_ws_per_fold(K, M, dtype == CVM_F64 ? 8 : 4, max_fold_rows) + 512;
+    const size_t small = (size_t)nb * small_ws_per_fold(K, M, esize_of(dtype), max_fold_rows) + 512;
     // (batches of folds of 8 rows or more may take mid_tile_kernel behind the statistics pre-pass: one
     //  statistics unit and one statistics vector per fold)
-    const Geom gs = make_geom(K, M, dtype == CVM_F64 ? 8 : 4, 1);
-    const size_t pre = (size_t)nb * (align_up(gs.stat_len * 8, 256) + align_up(fstat_len(K, M) * 8, 256));
+    const size_t pre = (size_t)nb * (stat_geom(K, M, esize_of(dtype)).unit_bytes + align_up(fstat_len(K, M) * 8, 256));
     return (small > pre ? small : pre) + QUEUE_RESERVE;
   }
-  const Geom g = make_geom(K, M, dtype == CVM_F64 ? 8 : 4, !(flags & CVM_RET_XTX));
-  const int splits = plan_stride(n_folds, max_fold_rows, g, dtype == CVM_F64 ? 8 : 4);
+  const Geom g = make_geom(K, M, esize_of(dtype), !(flags & CVM_RET_XTX));
+  const int splits = plan_stride(n_folds, max_fold_rows, g, esize_of(dtype));
   const size_t per_fold = (size_t)splits * g.unit_bytes + align_up(fstat_len(K, M) * 8, 256);
   size_t want = per_fold * (size_t)(n_folds > 0 ? n_folds : 1);
   const size_t cap = (size_t)8 << 30;   // beyond 8 GiB walk the folds in batches
@@ -135,17 +131,11 @@ int cvm_fold_update_ex(const void *X, const void *Y, const void *w, const int64_
   if ((flags & CVM_IDX_HOST) && (n_folds != 1 || host_offsets[1] - host_offsets[0] > SMALL_ROWS ||
                                 host_offsets[1] < host_offsets[0]))
     return fail(CVM_EINVAL, "cvm_fold_update: CVM_IDX_HOST takes one fold of at most 32 rows%s");
-  if (dtype == CVM_F64)
-    return fold_update_impl<double>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype,
-                                    flags, ddof, resolution, G, H, gstats, out_XTX, out_XTY, out_muX,
-                                    out_sdX, out_muY, out_sdY, out_fold, ws, ws_bytes,
-                                    (hipStream_t)stream, status);
-  if (dtype == CVM_F32)
-    return fold_update_impl<float>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype,
-                                   flags, ddof, resolution, G, H, gstats, out_XTX, out_XTY, out_muX,
-                                   out_sdX, out_muY, out_sdY, out_fold, ws, ws_bytes,
-                                   (hipStream_t)stream, status);
-  return fail(CVM_EINVAL, "cvm_fold_update: dtype must be CVM_F32 or CVM_F64%s");
+  const FoldCall c{X, Y, w, idx, offsets, N, K, M, flags, ddof, resolution, w != nullptr, G, H, gstats, out_XTX, out_XTY,
+                   out_muX, out_sdX, out_muY, out_sdY, out_fold, (flags & CVM_RET_XTY) && out_XTY, status};
+  return by_dtype(dtype, "cvm_fold_update", [&](auto t) {
+    return fold_update_impl<decltype(t)>(c, host_offsets, n_folds, dtype, ws, ws_bytes, (hipStream_t)stream);
+  });
 }
 
 int cvm_fold_update(const void *X, const void *Y, const void *w, const int64_t *idx,
@@ -211,8 +201,8 @@ int cvm_debug_stamps2(unsigned long long *host_out) {
 #endif
 
 size_t cvm_sweep_workspace_bytes(int64_t n_folds, int64_t max_fold_rows, int K, int M, int dtype) {
-  const Geom g = make_geom(K, M, dtype == CVM_F64 ? 8 : 4, 0);
-  const int splits = plan_stride(n_folds, max_fold_rows, g, dtype == CVM_F64 ? 8 : 4);
+  const Geom g = make_geom(K, M, esize_of(dtype), 0);
+  const int splits = plan_stride(n_folds, max_fold_rows, g, esize_of(dtype));
   return ((size_t)splits * g.unit_bytes + align_up(fstat_len(K, M) * 8, 256)) * (size_t)(n_folds > 0 ? n_folds : 1) +
          QUEUE_RESERVE;
 }
@@ -225,13 +215,10 @@ int cvm_sweep_fit(const void *X, const void *Y, const void *w, const int64_t *id
     return fail(CVM_EINVAL, "cvm_sweep_fit: null pointer%s");
   if (n_folds <= 0 || N <= 0 || K <= 0 || M < 0 || (M > 0 && (!Y || !H)) || (M == 0 && Y))
     return fail(CVM_EINVAL, "cvm_sweep_fit: bad shape%s");
-  if (dtype == CVM_F64)
-    return sweep_fit_impl<double>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, G, H,
-                                  gstats, neg_flag, ws, ws_bytes, (hipStream_t)stream, splits_out);
-  if (dtype == CVM_F32)
-    return sweep_fit_impl<float>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, G, H,
-                                 gstats, neg_flag, ws, ws_bytes, (hipStream_t)stream, splits_out);
-  return fail(CVM_EINVAL, "cvm_sweep_fit: dtype must be CVM_F32 or CVM_F64%s");
+  return by_dtype(dtype, "cvm_sweep_fit", [&](auto t) {
+    return sweep_fit_impl<decltype(t)>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, G, H, gstats, neg_flag,
+                                       ws, ws_bytes, (hipStream_t)stream, splits_out);
+  });
 }
 
 int cvm_sweep_all(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
@@ -244,15 +231,12 @@ int cvm_sweep_all(const void *X, const void *Y, const void *w, const int64_t *id
   if (n_folds <= 0 || N <= 0 || K <= 0 || M < 0 || (M > 0 && (!Y || !H)) || (M == 0 && Y))
     return fail(CVM_EINVAL, "cvm_sweep_all: bad shape%s");
   if ((flags & CVM_RET_XTY) && M == 0) return fail(CVM_EINVAL, "cvm_sweep_all: CVM_RET_XTY needs Y and H%s");
-  if (dtype == CVM_F64)
-    return sweep_all_impl<double>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, flags, ddof, resolution,
-                                  G, H, gstats, neg_flag, out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY,
-                                  out_fold, ws, ws_bytes, (hipStream_t)stream, splits_out);
-  if (dtype == CVM_F32)
-    return sweep_all_impl<float>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, flags, ddof, resolution,
-                                 G, H, gstats, neg_flag, out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY,
-                                 out_fold, ws, ws_bytes, (hipStream_t)stream, splits_out);
-  return fail(CVM_EINVAL, "cvm_sweep_all: dtype must be CVM_F32 or CVM_F64%s");
+  const FoldCall c{X, Y, w, idx, offsets, N, K, M, flags, ddof, resolution, w != nullptr, G, H, gstats, out_XTX, out_XTY,
+                   out_muX, out_sdX, out_muY, out_sdY, out_fold, (flags & CVM_RET_XTY) && out_XTY, nullptr};
+  return by_dtype(dtype, "cvm_sweep_all", [&](auto t) {
+    return sweep_all_impl<decltype(t)>(c, host_offsets, n_folds, dtype, G, H, gstats, neg_flag, ws, ws_bytes,
+                                       (hipStream_t)stream, splits_out);
+  });
 }
 
 int cvm_sweep_fold_range(const int64_t *offsets, int64_t n_total, int64_t fold0, int64_t n_folds, int K, int M,
@@ -265,15 +249,11 @@ int cvm_sweep_fold_range(const int64_t *offsets, int64_t n_total, int64_t fold0,
     return fail(CVM_EINVAL, "cvm_sweep_folds: bad shape%s");
   if ((flags & CVM_RET_XTY) && (M == 0 || !H))
     return fail(CVM_EINVAL, "cvm_sweep_folds: CVM_RET_XTY needs Y and H%s");
-  if (dtype == CVM_F64)
-    return sweep_folds_impl<double>(offsets, n_total, fold0, n_folds, K, M, dtype, flags, ddof, resolution, weighted,
-                                    G, H, gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold,
-                                    ws, ws_bytes, splits, (hipStream_t)stream);
-  if (dtype == CVM_F32)
-    return sweep_folds_impl<float>(offsets, n_total, fold0, n_folds, K, M, dtype, flags, ddof, resolution, weighted,
-                                   G, H, gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold,
-                                   ws, ws_bytes, splits, (hipStream_t)stream);
-  return fail(CVM_EINVAL, "cvm_sweep_folds: dtype must be CVM_F32 or CVM_F64%s");
+  const FoldCall c{nullptr, nullptr, nullptr, nullptr, offsets, 0, K, M, flags, ddof, resolution, weighted, G, H, gstats,
+                   out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold, (flags & CVM_RET_XTY) && out_XTY, nullptr};
+  return by_dtype(dtype, "cvm_sweep_folds", [&](auto t) {
+    return sweep_folds_impl<decltype(t)>(c, n_total, fold0, n_folds, ws, ws_bytes, splits, (hipStream_t)stream);
+  });
 }
 
 int cvm_sweep_folds(const int64_t *offsets, int64_t n_folds, int K, int M, int dtype, unsigned flags,
@@ -305,9 +285,8 @@ int cvm_sweep_unions(const int64_t *fold_offsets, int64_t n_total, const int64_t
   if ((flags & CVM_RET_XTX) && !out_XTX) return fail(CVM_EINVAL, "cvm_sweep_unions: CVM_RET_XTX needs out_XTX%s");
   if ((flags & CVM_RET_XTY) && (M == 0 || !H || !out_XTY))
     return fail(CVM_EINVAL, "cvm_sweep_unions: CVM_RET_XTY needs Y, H and out_XTY%s");
-  const int s_off = (int)(splits & 0xfffff), s_diag = (int)((splits >> 20) & 0xfffff);
-  if (splits <= 0 || (splits >> 41) != 0 || s_off < 1 || s_diag < 1)
-    return fail(CVM_EINVAL, "cvm_sweep_unions: not a plan token of cvm_sweep_fit%s");
+  PlanToken token;
+  if (!unpack_token(splits, token)) return fail(CVM_EINVAL, "cvm_sweep_unions: not a plan token of cvm_sweep_fit%s");
   if (host_union_offsets[0] < 0) return fail(CVM_EINVAL, "cvm_sweep_unions: negative union offset%s");
   for (int64_t u = 0; u < n_unions; ++u) {
     const int64_t n = host_union_offsets[u + 1] - host_union_offsets[u];
@@ -316,22 +295,18 @@ int cvm_sweep_unions(const int64_t *fold_offsets, int64_t n_total, const int64_t
     if (n > n_total) return fail(CVM_EINVAL, "cvm_sweep_unions: a union of more folds than the sweep has%s");
   }
   if (n_unions > 0 && (!union_folds || !union_offsets || !ws)) return fail(CVM_EINVAL, "cvm_sweep_unions: null pointer%s");
-  const int esize = dtype == CVM_F64 ? 8 : 4;
-  const Geom g = make_geom(K, M, esize, 0);
-  const size_t stride = (size_t)(s_off > s_diag ? s_off : s_diag);
+  const Geom g = make_geom(K, M, esize_of(dtype), 0);
+  const size_t stride = (size_t)(token.s_off > token.s_diag ? token.s_off : token.s_diag);
   if ((size_t)n_total * stride * g.unit_bytes > sweep_ws_bytes)
     return fail(CVM_EWORKSPACE, "cvm_sweep_unions: sweep workspace smaller than the one cvm_sweep_fit filled%s");
   if (union_workspace_bytes(n_unions, K, M) > ws_bytes)
     return fail(CVM_EWORKSPACE, "cvm_sweep_unions: workspace smaller than cvm_sweep_unions_workspace_bytes%s");
   if (n_unions == 0) return CVM_OK;
-  const bool compacted = (splits >> 40) & 1;
-  if (dtype == CVM_F64)
-    return sweep_unions_impl<double>(fold_offsets, union_folds, union_offsets, n_unions, g, s_off, s_diag, compacted, flags,
-                                     ddof, resolution, weighted, G, H, gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY,
-                                     out_sdY, out_fold, sweep_ws, ws, (hipStream_t)stream);
-  return sweep_unions_impl<float>(fold_offsets, union_folds, union_offsets, n_unions, g, s_off, s_diag, compacted, flags,
-                                  ddof, resolution, weighted, G, H, gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY,
-                                  out_sdY, out_fold, sweep_ws, ws, (hipStream_t)stream);
+  const FoldCall c{nullptr, nullptr, nullptr, nullptr, fold_offsets, 0, K, M, flags, ddof, resolution, weighted, G, H, gstats,
+                   out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold, (flags & CVM_RET_XTY) != 0, nullptr};
+  return by_dtype(dtype, "cvm_sweep_unions", [&](auto t) {
+    return sweep_unions_impl<decltype(t)>(c, union_folds, union_offsets, n_unions, g, token, sweep_ws, ws, (hipStream_t)stream);
+  });
 }
 
 size_t cvm_stream_workspace_bytes(int what, int64_t n_folds, int64_t max_fold_rows, int K, int M, int dtype) {
@@ -367,9 +342,9 @@ int cvm_stream_add(const void *X, const void *Y, const void *w, const int64_t *i
   if (const char *bad = stream_bad_state(state, n_folds, K, M, dtype)) return fail(CVM_EINVAL, bad);
   if (!acc || !host_offsets) return fail(CVM_EINVAL, "cvm_stream_add: null pointer%s");
   if (host_offsets[0] < 0) return fail(CVM_EINVAL, "cvm_stream_add: negative offset%s");
-  for (int64_t f = 0; f < n_folds; ++f)
-    if (host_offsets[f + 1] < host_offsets[f]) return fail(CVM_EINVAL, "cvm_stream_add: offsets must be non-decreasing%s");
-  if (host_offsets[n_folds] - host_offsets[0] != n_rows)
+  int64_t max_rows = 0, present = 0;
+  if (int bad = fold_rows(host_offsets, n_folds, "cvm_stream_add", &max_rows, &present)) return bad;
+  if (!folds_cover(host_offsets, n_folds, n_rows))
     return fail(CVM_EINVAL, "cvm_stream_add: the folds must cover each of the chunk's n_rows rows exactly once%s");
   if (stream_units_bytes(n_folds, K, M, 8) > acc_bytes)
     return fail(CVM_EWORKSPACE, "cvm_stream_add: accumulator smaller than cvm_stream_workspace_bytes(CVM_STREAM_ACCUMULATOR)%s");
@@ -380,11 +355,10 @@ int cvm_stream_add(const void *X, const void *Y, const void *w, const int64_t *i
   if (state[SS_WEIGHTED] >= 0 && state[SS_WEIGHTED] != (w != nullptr))
     return fail(CVM_EINVAL, "cvm_stream_add: every chunk of a stream has weights, or none has%s");
   // (a workspace too small for one slot per fold: CVM_EWORKSPACE from the plan, before the first launch)
-  if (dtype == CVM_F64)
-    return stream_add_impl<double>(X, Y, w, idx, offsets, host_offsets, n_folds, n_rows, K, M, dtype, acc, state, ws,
-                                   ws_bytes, (hipStream_t)stream, info);
-  return stream_add_impl<float>(X, Y, w, idx, offsets, host_offsets, n_folds, n_rows, K, M, dtype, acc, state, ws, ws_bytes,
-                                (hipStream_t)stream, info);
+  return by_dtype(dtype, "cvm_stream_add", [&](auto t) {
+    return stream_add_impl<decltype(t)>(X, Y, w, idx, offsets, max_rows, present, n_folds, n_rows, K, M, dtype, acc, state, ws,
+                                        ws_bytes, (hipStream_t)stream, info);
+  });
 }
 
 int cvm_stream_close(void *acc, size_t acc_bytes, const int64_t *state, int64_t n_folds, int K, int M, int dtype, void *G,
@@ -400,11 +374,11 @@ int cvm_stream_close(void *acc, size_t acc_bytes, const int64_t *state, int64_t 
     return fail(CVM_EWORKSPACE, "cvm_stream_close: accumulator smaller than cvm_stream_workspace_bytes(CVM_STREAM_ACCUMULATOR)%s");
   if (dtype == CVM_F32 && stream_units_bytes(n_folds, K, M, 4) > ws_bytes)
     return fail(CVM_EWORKSPACE, "cvm_stream_close: workspace smaller than cvm_stream_workspace_bytes(CVM_STREAM_CLOSE)%s");
-  if (units_bytes_out) *units_bytes_out = dtype == CVM_F64 ? stream_units_bytes(n_folds, K, M, 8) : stream_units_bytes(n_folds, K, M, 4);
-  if (splits_out) *splits_out = (int64_t)1 | ((int64_t)1 << 20);      // one slot per fold
-  if (dtype == CVM_F64)
-    return stream_close_impl<double>(acc, n_folds, K, M, G, H, gstats, neg_flag, ws, (hipStream_t)stream, units_out);
-  return stream_close_impl<float>(acc, n_folds, K, M, G, H, gstats, neg_flag, ws, (hipStream_t)stream, units_out);
+  if (units_bytes_out) *units_bytes_out = stream_units_bytes(n_folds, K, M, esize_of(dtype));
+  if (splits_out) *splits_out = pack_token(1, 1);      // one slot per fold
+  return by_dtype(dtype, "cvm_stream_close", [&](auto t) {
+    return stream_close_impl<decltype(t)>(acc, n_folds, K, M, G, H, gstats, neg_flag, ws, (hipStream_t)stream, units_out);
+  });
 }
 
 size_t cvm_partition_workspace_bytes(int64_t N, int64_t n_labels) { return partition_workspace_bytes(N, n_labels); }
@@ -435,7 +409,7 @@ int cvm_weights_check(const void *w, int64_t N, int dtype, int64_t *out2, void *
 
 size_t cvm_pls_workspace_bytes(int64_t n_folds, int K, int M, int A, int dtype) {
   if (n_folds < 0 || K <= 0 || M <= 0 || M > PLS_MAXM || A <= 0 || A > PLS_MAXA) return 0;
-  return pls_workspace_bytes(n_folds, K, M, A, dtype == CVM_F64 ? 8 : 4, pls_cu_count());
+  return pls_workspace_bytes(n_folds, K, M, A, esize_of(dtype), pls_cu_count());
 }
 
 int cvm_pls_fit(const void *XTX, const void *XTY, int64_t n_folds, int K, int M, int A, int dtype,
@@ -657,7 +631,7 @@ int cvm_cv_predict_plan(int64_t n_folds, int64_t max_fold_rows, int64_t ldX, int
                         int64_t *info) {
   if (!info) return fail(CVM_EINVAL, "cvm_cv_predict_plan: null pointer%s");
   if (const char *bad = predict_bad_shape(n_folds, max_fold_rows, ldX, K, M, A, dtype)) return fail(CVM_EINVAL, bad);
-  const int esize = dtype == CVM_F64 ? 8 : 4;
+  const int esize = esize_of(dtype);
   const void *where = aligned ? nullptr : reinterpret_cast<const void *>(8);      // (stands for every address)
   const TilePlan t = tile_plan(K, M, A, esize, tile_vec(16 / esize, where, ldX, K, M, where, where, where));
   const PredictPlan p = predict_plan(n_folds, max_fold_rows, t.groups);
@@ -671,11 +645,11 @@ int cvm_pls_plan(int64_t n_folds, int K, int M, int A, int dtype, int64_t *info)
   if (!info || n_folds < 0 || K <= 0 || M <= 0 || M > PLS_MAXM || A <= 0 || A > PLS_MAXA)
     return fail(CVM_EINVAL, "cvm_pls_plan: bad argument%s");
   PlsPlan p;
-  if (!make_pls_plan(n_folds, K, M, A, dtype == CVM_F64 ? 8 : 4, pls_cu_count(), p))
+  if (!make_pls_plan(n_folds, K, M, A, esize_of(dtype), pls_cu_count(), p))
     return fail(CVM_EINVAL, "cvm_pls_plan: K too large for the LDS plan%s");
   info[0] = p.S; info[1] = p.rows; info[2] = p.folds_per_launch; info[3] = p.xres; info[4] = (int64_t)p.lds;
   PlsRepPlan r;
-  if (make_pls_rep_plan(n_folds, K, M, A, dtype == CVM_F64 ? 8 : 4, pls_cu_count(), r)) {      // few folds: the one-barrier kernel
+  if (make_pls_rep_plan(n_folds, K, M, A, esize_of(dtype), pls_cu_count(), r)) {      // few folds: the one-barrier kernel
     info[0] = r.S; info[1] = r.rows; info[2] = r.folds_per_launch; info[3] = 2; info[4] = (int64_t)r.lds;
   }
   return CVM_OK;
@@ -789,7 +763,7 @@ int cvm_plan_fold(int64_t n_folds, int64_t max_fold_rows, int K, int M, int dtyp
   // kernel 36 (the upper triangle of its 8 x 8 grid) + 8 per 16 live columns of the first Y
   // chunk; in the general kernel, or when folds are finished in the epilogue, 3 blocks of 16 +
   // 16 for XTY
-  const int es_ = dtype == CVM_F64 ? 8 : 4;
+  const int es_ = esize_of(dtype);
   const bool tri = ((size_t)K * es_) % 16 == 0 && (es_ == 4 || M % 2 == 0) &&
                    !(es_ == 8 && fold_mode && p.splits == 1);
   if (!p.g.diag_only) per4 += (int64_t)(p.g.nTiles - p.g.P) * 64 + (int64_t)p.g.P * (tri ? 36 : 48);

@@ -261,26 +261,15 @@ inline size_t union_workspace_bytes(int64_t n_unions, int K, int M) {
 }
 
 template <typename T>
-int sweep_unions_impl(const int64_t *fold_offsets, const int64_t *union_folds, const int64_t *union_offsets,
-                      int64_t n_unions, const Geom &g, int s_off, int s_diag, bool compacted, unsigned flags, double ddof,
-                      double resolution, int weighted, const void *G, const void *H, const double *gstats, void *out_XTX,
-                      void *out_XTY, void *out_muX, void *out_sdX, void *out_muY, void *out_sdY, double *out_fold,
-                      const void *sweep_ws, void *ws, hipStream_t st) {
+int sweep_unions_impl(const FoldCall &c, const int64_t *union_folds, const int64_t *union_offsets, int64_t n_unions,
+                      const Geom &g, const PlanToken &token, const void *sweep_ws, void *ws, hipStream_t st) {
   const int K = g.K, M = g.M;
   Plan p;
   p.g = g;
-  set_plan_splits(p, s_off, s_diag);
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = g; set_fin_splits(f, p, 1);
-  if (compacted) f.s_off = f.s_diag = 1;          // (f.splits stays the slot stride)
-  f.ws = (const char *)sweep_ws;
-  f.offs = fold_offsets; f.w = weighted ? (const void *)G : nullptr;   // non-null = weighted
-  f.G = G; f.H = H; f.gstats = gstats;
-  f.out_XTX = (flags & CVM_RET_XTX) ? out_XTX : nullptr;
-  f.out_XTY = (flags & CVM_RET_XTY) ? out_XTY : nullptr;
-  f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
-  f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
+  set_plan_splits(p, token.s_off, token.s_diag);
+  FinArgs f = fin_base(p, 1, 0, 0, sweep_ws);     // (segments: set per launch)
+  if (token.compacted) f.s_off = f.s_diag = 1;    // (f.splits stays the slot stride)
+  fin_fold_side(f, c);
   f.gx = g.nTiles * APPLY_SUB + g.P;
   const bool mats = f.out_XTX || f.out_XTY;
   const int64_t per_launch = (UNION_MAX_WGS - 7) / f.gx > 0 ? (UNION_MAX_WGS - 7) / f.gx : 1;

@@ -45,6 +45,14 @@ inline TimedLaunch *timed_begin(int kind, hipStream_t st) {
   return tl;
 }
 inline void timed_end(TimedLaunch *tl, hipStream_t st) { if (tl) (void)hipEventRecord(tl->b, st); }
+// the pair around a scope that may be left early (kind < 0: not recorded)
+struct TimedScope {
+  TimedLaunch *tl; hipStream_t st;
+  TimedScope(int kind, hipStream_t s) : tl(kind >= 0 ? timed_begin(kind, s) : nullptr), st(s) {}
+  ~TimedScope() { timed_end(tl, st); }
+  TimedScope(const TimedScope &) = delete;
+  TimedScope &operator=(const TimedScope &) = delete;
+};
 enum { KIND_FIT = 0, KIND_FOLD = 1, KIND_STREAM = 4, N_KINDS = 5 };
 
 // ---- optional clock probe of the product Gram kernel (cvm_clock_probe) -------------------
@@ -275,7 +283,7 @@ void set_plan_splits(Plan &p, int s_off, int s_diag) {
 
 int make_plan(int64_t n_folds, int64_t max_rows, int K, int M, int dtype, unsigned flags,
               size_t ws_bytes, bool fold_mode, Plan &p) {
-  const int esize = dtype == CVM_F64 ? 8 : 4;
+  const int esize = esize_of(dtype);
   const int diag_only = fold_mode && !(flags & CVM_RET_XTX);
   p.g = make_geom(K, M, esize, diag_only);
   const SplitChoice c = choose_splits2(n_folds, max_rows, p.g, esize, target_wg(K, M, esize));
@@ -305,12 +313,66 @@ void set_fin_splits(FinArgs &f, const Plan &p, int n_sum) {
 }
 
 // can this problem take the float64 LDS-DMA kernel (wgram4_kernel)?
-template <typename T> bool wgram4_ok(const WgramArgs<T> &a, bool aligned) {
-  static const bool force_fallback = getenv("CVM_FORCE_FALLBACK") && atoi(getenv("CVM_FORCE_FALLBACK")) != 0;
-  if (force_fallback || !aligned) return false;   // aligned: X and its rows on 16-byte boundaries
+template <typename T> bool wgram4_ok(int M, const void *Y, const void *w, bool aligned) {
+  if (fold_switches().force_fallback || !aligned) return false;   // aligned: X and its rows on 16-byte boundaries
   if (sizeof(T) == 8)   // the Y tile rows go by 16-byte pieces too: M even, Y 16-byte aligned
-    return (a.g.M % 2 == 0) && ((uintptr_t)a.Y % 16 == 0) && ((uintptr_t)a.w % 8 == 0);
-  return ((uintptr_t)a.Y % 4 == 0) && ((uintptr_t)a.w % 4 == 0);   // float32: Y and w by dwords
+    return (M % 2 == 0) && ((uintptr_t)Y % 16 == 0) && ((uintptr_t)w % 8 == 0);
+  return ((uintptr_t)Y % 4 == 0) && ((uintptr_t)w % 4 == 0);   // float32: Y and w by dwords
+}
+
+// ---- the argument records, each filled in one place ------------------------------------------
+// a Gram launch over n_seg segments from seg0 on (everything a plain launch does not set is zero)
+template <typename T>
+WgramArgs<T> gram_args(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offs, int64_t N,
+                       int64_t seg0, const Plan &p, int64_t n_seg, void *ws) {
+  WgramArgs<T> a;
+  memset(&a, 0, sizeof(a));
+  a.X = (const T *)X; a.Y = (const T *)Y; a.w = (const T *)w;
+  a.idx = idx; a.offs = offs; a.N = N; a.seg0 = seg0;
+  set_items(a, p, n_seg);
+  a.ws = (char *)ws;
+  return a;
+}
+// a finalize launch over n_seg segments from seg0 on: geometry, splits, where the partials lie
+inline FinArgs fin_base(const Plan &p, int n_sum, int64_t n_seg, int64_t seg0, const void *ws) {
+  FinArgs f;
+  memset(&f, 0, sizeof(f));
+  f.g = p.g; set_fin_splits(f, p, n_sum); f.n_seg = (int)n_seg; f.seg0 = seg0; f.ws = (const char *)ws;
+  return f;
+}
+// ... that sums the partials into the full-data matrices (fit_apply_kernel and its kin)
+inline void fin_fit_side(FinArgs &f, const void *w, void *G, void *H, int32_t *neg_flag) {
+  f.w = w; f.out_XTX = G; f.out_XTY = H; f.neg_flag = neg_flag;
+}
+
+// what the kernels of one fold-stage call are handed: the call's own arguments, typed once by the entry
+// (cvm_fold_update, cvm_sweep_folds / _fold_range, cvm_sweep_all, cvm_sweep_unions; what an entry has not is null)
+struct FoldCall {
+  const void *X, *Y, *w;
+  const int64_t *idx, *offsets;
+  int64_t N;
+  int K, M;
+  unsigned flags;
+  double ddof, resolution;
+  int weighted;                // the sweep's calls have no w: they are told
+  const void *G, *H;
+  const double *gstats;
+  void *out_XTX, *out_XTY, *out_muX, *out_sdX, *out_muY, *out_sdY;
+  double *out_fold;
+  bool want_xty;               // CVM_RET_XTY and somewhere to put it
+  int32_t *status;
+};
+// ... that forms the folds' statistics (and, `mats`, their matrices from G and H).  The kernels only ask whether
+// f.w is null: a weighted call without w (the sweep) passes G.
+inline void fin_fold_side(FinArgs &f, const FoldCall &c, bool mats = true) {
+  f.offs = c.offsets; f.w = c.w ? c.w : (c.weighted ? c.G : nullptr); f.gstats = c.gstats;
+  if (mats) {
+    f.G = c.G; f.H = c.H;
+    f.out_XTX = (c.flags & CVM_RET_XTX) ? c.out_XTX : nullptr;
+    f.out_XTY = (c.flags & CVM_RET_XTY) ? c.out_XTY : nullptr;
+  }
+  f.out_muX = c.out_muX; f.out_sdX = c.out_sdX; f.out_muY = c.out_muY; f.out_sdY = c.out_sdY;
+  f.out_fold = c.out_fold; f.ddof = c.ddof; f.resolution = c.resolution; f.flags = c.flags;
 }
 
 // (Earlier versions kept the queue heads in the last QUEUE_BYTES of the caller's workspace: the
@@ -468,17 +530,8 @@ int launch_wgram(const WgramArgs<T> &a, bool weighted, bool gather, bool aligned
     }                                                                                      \
     hipLaunchKernelGGL((wgram_kernel<T, W, GA, AL>), grid, block, lds, st, args);          \
   } while (0)
-  TimedLaunch *tl = nullptr;
-  if (kind >= 0 && g_timing.load(std::memory_order_relaxed)) {
-    std::lock_guard<std::mutex> lk(g_timing_mu);
-    if (g_ntimed < MAX_TIMED) {
-      tl = &g_timed[g_ntimed++];
-      if (!tl->a) { HIP_OK(hipEventCreate(&tl->a)); HIP_OK(hipEventCreate(&tl->b)); }
-      tl->kind = kind;
-    }
-  }
-  if (tl) HIP_OK(hipEventRecord(tl->a, st));
-  const bool fast = wgram4_ok<T>(a, aligned) && !(dbg_env & 16);
+  TimedScope timed(kind, st);       // (its end event goes behind the launch when the function returns)
+  const bool fast = wgram4_ok<T>(a.g.M, a.Y, a.w, aligned) && !(dbg_env & 16);
   if (fused && !(fast && gather))
     return fail(CVM_EINVAL, "launch_wgram: fused epilogue needs the LDS-DMA kernel%s");
   if (fast) {
@@ -529,7 +582,6 @@ int launch_wgram(const WgramArgs<T> &a, bool weighted, bool gather, bool aligned
     else { if (aligned) CVM_LAUNCH(false, false, true); else CVM_LAUNCH(false, false, false); }
   }
 #undef CVM_LAUNCH
-  if (tl) HIP_OK(hipEventRecord(tl->b, st));
   HIP_OK(hipGetLastError());
   return CVM_OK;
 }
@@ -564,18 +616,11 @@ int gram_fit_impl(const void *X, const void *Y, const void *w, int64_t N, int K,
   Plan p;
   int rc = make_plan(1, N, K, M, dtype, CVM_RET_XTX | CVM_RET_XTY, ws_bytes, false, p);
   if (rc != CVM_OK) return fail(rc, "cvm_gram_fit: workspace too small%s");
-  WgramArgs<T> a;
-  memset(&a, 0, sizeof(a));
-  a.X = (const T *)X; a.Y = (const T *)Y; a.w = (const T *)w;
-  a.idx = nullptr; a.offs = nullptr; a.N = N; a.seg0 = 0;
-  set_items(a, p, 1);
-  a.ws = (char *)ws;
-  rc = launch_wgram<T>(a, w != nullptr, false, rows_aligned(X, K, sizeof(T)), st, KIND_FIT, wq.queue);
+  rc = launch_wgram<T>(gram_args<T>(X, Y, w, nullptr, nullptr, N, 0, p, 1, ws), w != nullptr, false,
+                       rows_aligned(X, K, sizeof(T)), st, KIND_FIT, wq.queue);
   if (rc != CVM_OK) return rc;
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = p.g; set_fin_splits(f, p, 1); f.n_seg = 1; f.seg0 = 0; f.ws = (const char *)ws;
-  f.w = w; f.out_XTX = G; f.out_XTY = (Y && M > 0) ? H : nullptr; f.neg_flag = neg_flag;
+  FinArgs f = fin_base(p, 1, 1, 0, ws);
+  fin_fit_side(f, w, G, (Y && M > 0) ? H : nullptr, neg_flag);
   launch_fit_apply<T>(f, p.g, gstats, st);
   HIP_OK(hipGetLastError());
   return CVM_OK;
@@ -629,41 +674,35 @@ inline size_t small_ws_per_fold(int K, int M, int esize, int64_t max_rows) {
   return align_up(fstat_len(K, M) * 8, 256) + (res_shape_ok(K, esize, max_rows) ? res_pack_bytes(K, max_rows) : 0);
 }
 int small_route_limit(int K, int esize) {
-  static const int forced = [] {
-    const char *e = getenv("CVM_SMALL_MAXN");
-    int v = e ? atoi(e) : 0;
-    if (e && v < SMALL_ROWS) v = SMALL_ROWS;
-    if (v > SMALL_MAXN) v = SMALL_MAXN;
-    return v;
-  }();
-  if (forced) return forced;
+  static_assert(SWITCH_SMALL_LO == SMALL_ROWS && SWITCH_SMALL_HI == SMALL_MAXN, "CVM_SMALL_MAXN is clamped to the kernels' limits");
+  if (const int forced = fold_switches().small_maxn) return forced;
   if (esize == 4) return K < 768 ? 48 : 64;
   return K < 768 ? SMALL_ROWS : (K < 4096 ? 48 : SMALL_MAXN);
 }
 
 template <typename T>
-int small_fold_impl(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
-                    int64_t n_folds, int64_t max_rows, int K, int M, unsigned flags, double ddof, double resolution,
-                    const void *G, const void *H, const double *gstats, void *out_XTX, void *out_XTY,
-                    void *out_muX, void *out_sdX, void *out_muY, void *out_sdY, double *out_fold,
-                    void *ws, size_t ws_bytes, hipStream_t st) {
+int small_fold_impl(const FoldCall &c, int64_t n_folds, int64_t max_rows, void *ws, size_t ws_bytes, hipStream_t st) {
+  const void *const X = c.X, *const w = c.w, *const G = c.G;
+  const int64_t *const idx = c.idx, *const offsets = c.offsets;
+  const int K = c.K, M = c.M;
+  const unsigned flags = c.flags;
   // per fold: the float64 statistics vector
   const size_t per_fold = small_ws_per_fold(K, M, (int)sizeof(T), max_rows);
   int64_t nb_max = (int64_t)((ws_bytes > 256 ? ws_bytes - 256 : 0) / per_fold);
   if (nb_max < 1) return fail(CVM_EWORKSPACE, "cvm_fold_update: workspace cannot hold one fold%s");
   if (nb_max > 32768) nb_max = 32768;   // grid.y
   if (nb_max > n_folds) nb_max = n_folds;
-  static const bool no_direct = getenv("CVM_NO_DIRECT") != nullptr;   // tests: force the transposing kernel
+  const bool no_direct = fold_switches().no_direct;   // tests: force the transposing kernel
   SmallArgs a;
   memset(&a, 0, sizeof(a));
-  a.X = X; a.Y = Y; a.w = w; a.idx = idx; a.offs = offsets; a.K = K; a.M = M;
-  a.G = G; a.H = H; a.gstats = gstats; a.fstats = (double *)ws;
+  a.X = X; a.Y = c.Y; a.w = w; a.idx = idx; a.offs = offsets; a.K = K; a.M = M;
+  a.G = G; a.H = c.H; a.gstats = c.gstats; a.fstats = (double *)ws;
   // (round 4's accumulator-direct tile kernel -- small_tile_kernel, CVM_SMALL_TILE -- was measured slower than the
   //  kernels below and left the product in round 6: tools/experiments/pruned_r6_routes.patch)
-  a.out_XTX = (flags & CVM_RET_XTX) ? out_XTX : nullptr;
-  a.out_XTY = (flags & CVM_RET_XTY) ? out_XTY : nullptr;
-  a.out_muX = out_muX; a.out_sdX = out_sdX; a.out_muY = out_muY; a.out_sdY = out_sdY;
-  a.out_fold = out_fold; a.ddof = ddof; a.resolution = resolution; a.flags = flags;
+  a.out_XTX = (flags & CVM_RET_XTX) ? c.out_XTX : nullptr;
+  a.out_XTY = (flags & CVM_RET_XTY) ? c.out_XTY : nullptr;
+  a.out_muX = c.out_muX; a.out_sdX = c.out_sdX; a.out_muY = c.out_muY; a.out_sdY = c.out_sdY;
+  a.out_fold = c.out_fold; a.ddof = c.ddof; a.resolution = c.resolution; a.flags = flags;
   a.P64 = (K + ST - 1) / ST; a.nT64 = a.P64 * (a.P64 + 1) / 2;
   a.inl_n = -1;
   if (flags & CVM_IDX_HOST) {            // one fold, indices on the host: into the kernel arguments
@@ -828,117 +867,79 @@ template <typename T> int launch_mid(MidArgs m, bool weighted, int64_t nb, int64
   return CVM_OK;
 }
 
-// statistics-only fold stage: colstats_kernel + fold_stats_kernel, no Gram launch
-template <typename T>
-int fold_statistics_impl(const void *X, const void *Y, const void *w, const int64_t *idx,
-                         const int64_t *offsets, int64_t n_folds, int64_t max_rows, int K, int M,
-                         unsigned flags, double ddof, double resolution, const double *gstats,
-                         void *out_muX, void *out_sdX, void *out_muY, void *out_sdY, double *out_fold,
-                         void *ws, size_t ws_bytes, hipStream_t st) {
-  Geom g = make_geom(K, M, sizeof(T), 1);
+// ---- the statistics pre-pass: colstats_kernel + fold_stats_kernel, no Gram launch ------------------
+// its geometry: a unit per (fold, row split) holds the column sums alone
+inline Geom stat_geom(int K, int M, int esize) {
+  Geom g = make_geom(K, M, esize, 1);
   g.tile_elems = 0; g.h_elems = 0;
   g.unit_bytes = align_up(g.stat_len * 8, 256);
-  const size_t fst = align_up(fstat_len(K, M) * 8, 256);
-  int64_t splits = colstats_splits(max_rows, n_folds, K, sizeof(T), current_cu_count());
-  while (splits > 1 && (size_t)splits * g.unit_bytes + fst > ws_bytes) splits /= 2;
-  const size_t per_fold = (size_t)splits * g.unit_bytes + fst;
-  if (per_fold > ws_bytes) return fail(CVM_EWORKSPACE, "cvm_fold_update: workspace cannot hold one fold%s");
-  int64_t per_batch = (int64_t)(ws_bytes / per_fold);
-  if (per_batch > 32768) per_batch = 32768;
-  const bool aligned = rows_aligned(X, K, sizeof(T));
-  for (int64_t f0 = 0; f0 < n_folds; f0 += per_batch) {
-    const int64_t nb = (n_folds - f0 < per_batch) ? n_folds - f0 : per_batch;
-    ColArgs c;
-    c.X = X; c.Y = Y; c.w = w; c.idx = idx; c.offs = offsets; c.seg0 = f0;
-    c.g = g; c.ws = (char *)ws;
-    colstats_shape<T>(c, K, M, nb, (int)splits);
-    const dim3 grid = colstats_grid(c, nb);
-    if (w) {
-      if (aligned) hipLaunchKernelGGL((colstats_kernel<T, true, true>), grid, dim3(COL_THREADS), 0, st, c);
-      else hipLaunchKernelGGL((colstats_kernel<T, true, false>), grid, dim3(COL_THREADS), 0, st, c);
-    } else {
-      if (aligned) hipLaunchKernelGGL((colstats_kernel<T, false, true>), grid, dim3(COL_THREADS), 0, st, c);
-      else hipLaunchKernelGGL((colstats_kernel<T, false, false>), grid, dim3(COL_THREADS), 0, st, c);
-    }
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.g = g; f.splits = f.s_off = f.s_diag = (int)splits; f.n_sum = 1;
-    f.n_seg = (int)nb; f.seg0 = f0; f.ws = (const char *)ws;
-    f.fstats = (double *)((char *)ws + (size_t)nb * splits * g.unit_bytes);
-    f.offs = offsets; f.w = w; f.gstats = gstats;
-    f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
-    f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
-    hipLaunchKernelGGL((fold_stats_kernel<T>), dim3((unsigned)nb, (unsigned)fold_stats_chunks(K, M, nb)), dim3(256), 0, st, f);
+  return g;
+}
+// ... and its plan: row splits (halved until a fold fits the workspace), a fold's statistics vector and all its
+// bytes, folds per batch (0: the workspace cannot hold one fold -- the caller says so)
+struct StatPlan { Plan p; size_t fst, per_fold; int64_t per_batch; };
+inline StatPlan stat_plan(int K, int M, int esize, int64_t max_rows, int64_t n_folds, size_t ws_bytes, int64_t batch_cap) {
+  StatPlan s;
+  s.p.g = stat_geom(K, M, esize);
+  s.p.folds_per_batch = 0; s.p.fstat_bytes_per_fold = 0;
+  s.fst = align_up(fstat_len(K, M) * 8, 256);
+  int64_t splits = colstats_splits(max_rows, n_folds, K, (size_t)esize, current_cu_count());
+  while (splits > 1 && (size_t)splits * s.p.g.unit_bytes + s.fst > ws_bytes) splits /= 2;
+  set_plan_splits(s.p, (int)splits, (int)splits);
+  s.per_fold = (size_t)splits * s.p.g.unit_bytes + s.fst;
+  s.per_batch = (int64_t)(ws_bytes / s.per_fold);
+  if (s.per_batch > batch_cap) s.per_batch = batch_cap;
+  return s;
+}
+// ... over the folds [f0, f0 + nb); returns where the folds' statistics vectors lie in ws
+template <typename T>
+double *launch_prepass(const FoldCall &c, const StatPlan &sp, bool aligned, int64_t f0, int64_t nb, void *ws, hipStream_t st) {
+  const Geom &gs = sp.p.g;
+  ColArgs ca;
+  ca.X = c.X; ca.Y = c.Y; ca.w = c.w; ca.idx = c.idx; ca.offs = c.offsets; ca.seg0 = f0;
+  ca.g = gs; ca.ws = (char *)ws;
+  colstats_shape<T>(ca, c.K, c.M, nb, sp.p.splits);
+  const dim3 cgrid = colstats_grid(ca, nb);
+  if (c.w) {
+    if (aligned) hipLaunchKernelGGL((colstats_kernel<T, true, true>), cgrid, dim3(COL_THREADS), 0, st, ca);
+    else hipLaunchKernelGGL((colstats_kernel<T, true, false>), cgrid, dim3(COL_THREADS), 0, st, ca);
+  } else {
+    if (aligned) hipLaunchKernelGGL((colstats_kernel<T, false, true>), cgrid, dim3(COL_THREADS), 0, st, ca);
+    else hipLaunchKernelGGL((colstats_kernel<T, false, false>), cgrid, dim3(COL_THREADS), 0, st, ca);
+  }
+  FinArgs f = fin_base(sp.p, 1, nb, f0, ws);
+  f.fstats = (double *)((char *)ws + (size_t)nb * sp.p.splits * gs.unit_bytes);
+  fin_fold_side(f, c, false);
+  hipLaunchKernelGGL((fold_stats_kernel<T>), dim3((unsigned)nb, (unsigned)fold_stats_chunks(c.K, c.M, nb)),
+                     dim3(256), 0, st, f);
+  return f.fstats;
+}
+
+// statistics-only fold stage: the pre-pass alone, batch by batch
+template <typename T>
+int fold_statistics_impl(const FoldCall &c, int64_t n_folds, int64_t max_rows, void *ws, size_t ws_bytes, hipStream_t st) {
+  const StatPlan sp = stat_plan(c.K, c.M, sizeof(T), max_rows, n_folds, ws_bytes, 32768);
+  if (sp.per_fold > ws_bytes) return fail(CVM_EWORKSPACE, "cvm_fold_update: workspace cannot hold one fold%s");
+  const bool aligned = rows_aligned(c.X, c.K, sizeof(T));
+  for (int64_t f0 = 0; f0 < n_folds; f0 += sp.per_batch) {
+    const int64_t nb = (n_folds - f0 < sp.per_batch) ? n_folds - f0 : sp.per_batch;
+    launch_prepass<T>(c, sp, aligned, f0, nb, ws, st);
     HIP_OK(hipGetLastError());
   }
   return CVM_OK;
 }
 
-// Route switches of the fold stage: read from the environment ONCE, in one place (tests, tools/route_matrix.sh
-// and the experiment scripts set them; none is needed in production).
-struct FoldSwitches {
-  int mid_minn, mid_maxn;      // CVM_MID_MINN / CVM_MID_MAXN: row limits of mid_tile_kernel (0: the measured table)
-  bool mid_off;                // CVM_MID_TILE=0: never mid_tile_kernel
-  bool force_fallback;         // CVM_FORCE_FALLBACK=1: the general Gram kernel
-  bool no_fused;               // CVM_NO_FUSED=1: partials + apply_kernel for one-unit folds too
-  bool prepass;                // CVM_FUSED_PREPASS=1: statistics by colstats_kernel + fold_stats_kernel, not in the launch
-  int fused_order;             // CVM_FUSED_ORDER: 2 = fold-major lists (default), 1 = every list's diagonal items first
-  int fused_test;              // CVM_FUSED_TEST_TIMEOUT: WgramArgs::test_mode
-};
-const FoldSwitches &fold_switches() {
-  static const FoldSwitches sw = [] {
-    auto num = [](const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; };
-    FoldSwitches f;
-    f.mid_minn = num("CVM_MID_MINN", 0); f.mid_maxn = num("CVM_MID_MAXN", 0);
-    f.mid_off = num("CVM_MID_TILE", 1) == 0;
-    f.force_fallback = num("CVM_FORCE_FALLBACK", 0) != 0;
-    f.no_fused = num("CVM_NO_FUSED", 0) != 0;
-    f.prepass = num("CVM_FUSED_PREPASS", 0) != 0;
-    f.fused_order = num("CVM_FUSED_ORDER", 2) == 1 ? 1 : 2;
-    f.fused_test = num("CVM_FUSED_TEST_TIMEOUT", 0);
-    return f;
-  }();
-  return sw;
-}
-
-// what every kernel of one cvm_fold_update call is handed (the call's own arguments, typed once)
-struct FoldCall {
-  const void *X, *Y, *w;
-  const int64_t *idx, *offsets;
-  int64_t N;
-  int K, M;
-  unsigned flags;
-  double ddof, resolution;
-  const void *G, *H;
-  const double *gstats;
-  void *out_XTX, *out_XTY, *out_muX, *out_sdX, *out_muY, *out_sdY;
-  double *out_fold;
-  bool want_xty;
-  int32_t *status;
-};
-
-// the statistics pre-pass over the folds [f0, f0 + nb): colstats_kernel + fold_stats_kernel; returns where the
-// folds' statistics vectors lie in ws
-template <typename T>
-double *launch_prepass(const FoldCall &c, const Geom &gs, int64_t csplits, int64_t f0, int64_t nb, void *ws, hipStream_t st) {
-  ColArgs ca;
-  ca.X = c.X; ca.Y = c.Y; ca.w = c.w; ca.idx = c.idx; ca.offs = c.offsets; ca.seg0 = f0;
-  ca.g = gs; ca.ws = (char *)ws;
-  colstats_shape<T>(ca, c.K, c.M, nb, (int)csplits);
-  const dim3 cgrid = colstats_grid(ca, nb);
-  if (c.w) hipLaunchKernelGGL((colstats_kernel<T, true, true>), cgrid, dim3(COL_THREADS), 0, st, ca);
-  else hipLaunchKernelGGL((colstats_kernel<T, false, true>), cgrid, dim3(COL_THREADS), 0, st, ca);
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = gs; f.splits = f.s_off = f.s_diag = (int)csplits; f.n_sum = 1;
-  f.n_seg = (int)nb; f.seg0 = f0; f.ws = (const char *)ws;
-  f.fstats = (double *)((char *)ws + (size_t)nb * csplits * gs.unit_bytes);
-  f.offs = c.offsets; f.w = c.w; f.gstats = c.gstats;
-  f.out_muX = c.out_muX; f.out_sdX = c.out_sdX; f.out_muY = c.out_muY; f.out_sdY = c.out_sdY;
-  f.out_fold = c.out_fold; f.ddof = c.ddof; f.resolution = c.resolution; f.flags = c.flags;
-  hipLaunchKernelGGL((fold_stats_kernel<T>), dim3((unsigned)nb, (unsigned)fold_stats_chunks(c.K, c.M, nb)),
-                     dim3(256), 0, st, f);
-  return f.fstats;
+// the fold statistics (unless apply_kernel forms them itself: FinArgs::inline_stats) and, where matrices are
+// wanted, the folds' matrices from the partials of n_folds folds
+template <typename T> void launch_fold_finalize(FinArgs f, int64_t n_folds, hipStream_t st) {
+  const Geom &g = f.g;
+  if (!f.inline_stats)
+    hipLaunchKernelGGL((fold_stats_kernel<T>), dim3((unsigned)n_folds, (unsigned)fold_stats_chunks(g.K, g.M, n_folds)), dim3(256), 0, st, f);
+  if (f.out_XTX || f.out_XTY) {
+    f.gx = g.nTiles * APPLY_SUB + g.P; f.gy = (int)n_folds;
+    hipLaunchKernelGGL((apply_kernel<T, true>), dim3((unsigned)(8 * (((size_t)f.gx * f.gy + 7) / 8))),
+                       dim3(APPLY_THREADS), 0, st, f);
+  }
 }
 
 // arguments of mid_tile_kernel over the folds [f0, ...) (fstats: from the pre-pass)
@@ -953,15 +954,10 @@ inline MidArgs mid_args(const FoldCall &c, int64_t f0, const double *fstats) {
   return m;
 }
 
-// arguments of a fused launch (wgram4_kernel<.., FUSED>, one unit per fold) over the folds [f0, f0 + nb)
+// arguments of a fused launch (wgram4_kernel<.., FUSED>, one unit per fold, no partials) over the folds [f0, f0 + nb)
 template <typename T>
 WgramArgs<T> fused_args(const FoldCall &c, const Plan &p, int64_t f0, int64_t nb, const double *fstats) {
-  WgramArgs<T> a;
-  memset(&a, 0, sizeof(a));
-  a.X = (const T *)c.X; a.Y = (const T *)c.Y; a.w = (const T *)c.w;
-  a.idx = c.idx; a.offs = c.offsets; a.N = c.N; a.seg0 = f0;
-  set_items(a, p, nb);               // (one unit per fold: p.s_off == p.s_diag == 1)
-  a.ws = nullptr;
+  WgramArgs<T> a = gram_args<T>(c.X, c.Y, c.w, c.idx, c.offsets, c.N, f0, p, nb, nullptr);   // (p.s_off == p.s_diag == 1)
   a.fstats = fstats; a.G = c.G; a.H = c.H;
   a.out_XTX = c.out_XTX; a.out_XTY = c.want_xty ? c.out_XTY : nullptr; a.flags = c.flags;
   if (fold_switches().fused_order == 2) {
@@ -975,18 +971,12 @@ WgramArgs<T> fused_args(const FoldCall &c, const Plan &p, int64_t f0, int64_t nb
 }
 
 template <typename T>
-int fold_update_impl(const void *X, const void *Y, const void *w, const int64_t *idx,
-                     const int64_t *offsets, const int64_t *host_offsets, int64_t n_folds, int64_t N,
-                     int K, int M, int dtype, unsigned flags, double ddof, double resolution,
-                     const void *G, const void *H, const double *gstats, void *out_XTX,
-                     void *out_XTY, void *out_muX, void *out_sdX, void *out_muY, void *out_sdY,
-                     double *out_fold, void *ws, size_t ws_bytes, hipStream_t st, int32_t *status) {
+int fold_update_impl(const FoldCall &c, const int64_t *host_offsets, int64_t n_folds, int dtype, void *ws, size_t ws_bytes,
+                     hipStream_t st) {
+  const int K = c.K, M = c.M;
+  const unsigned flags = c.flags;
   int64_t max_rows = 0;
-  for (int64_t f = 0; f < n_folds; ++f) {
-    const int64_t n = host_offsets[f + 1] - host_offsets[f];
-    if (n < 0) return fail(CVM_EINVAL, "cvm_fold_update: offsets must be non-decreasing%s");
-    if (n > max_rows) max_rows = n;
-  }
+  if (int bad = fold_rows(host_offsets, n_folds, "cvm_fold_update", &max_rows, nullptr)) return bad;
   const WsCarve wq = carve_queue(ws, ws_bytes);
   ws_bytes = wq.usable;
   const FoldSwitches &sw = fold_switches();
@@ -996,8 +986,9 @@ int fold_update_impl(const void *X, const void *Y, const void *w, const int64_t 
   const int mid_maxn = sw.mid_maxn > 0 ? sw.mid_maxn : mid_default_maxn(K, esize);
   // (... only where that kernel can run -- the conditions of the fused route below; a fold whose indices come
   //  inside the call -- CVM_IDX_HOST, one fold of at most 32 rows -- is the small route's)
-  const bool skip_small = !(flags & CVM_IDX_HOST) && max_rows >= mid_minn && ((flags & CVM_RET_XTX) && out_XTX) &&
-                          max_rows <= mid_maxn && mid_operands_ok<T>(X, Y, w, N, K, M) && !sw.force_fallback && !sw.no_fused;
+  const bool want_xtx = (flags & CVM_RET_XTX) && c.out_XTX;
+  const bool skip_small = !(flags & CVM_IDX_HOST) && max_rows >= mid_minn && want_xtx &&
+                          max_rows <= mid_maxn && mid_operands_ok<T>(c.X, c.Y, c.w, c.N, K, M) && !sw.force_fallback && !sw.no_fused;
   // (... and only if the fold stage is planned with one unit per fold -- always, unless a test forces a split plan)
   bool skip_small_ok = skip_small;
   // (round 6: float32 batches the resident route takes -- K a multiple of 1024, folds of at most 16 rows -- stay small folds)
@@ -1007,113 +998,79 @@ int fold_update_impl(const void *X, const void *Y, const void *w, const int64_t 
     if (make_plan(n_folds, max_rows, K, M, dtype, flags, (size_t)1 << 60, true, pp) != CVM_OK || pp.splits != 1) skip_small_ok = false;
   }
   if (max_rows <= small_route_limit(K, esize) && !skip_small_ok)
-    return small_fold_impl<T>(X, Y, w, idx, offsets, n_folds, max_rows, K, M, flags, ddof, resolution, G, H, gstats,
-                              out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold, ws, ws_bytes, st);
-  const bool want_xtx = (flags & CVM_RET_XTX) && out_XTX, want_xty = (flags & CVM_RET_XTY) && out_XTY;
-  if (!want_xtx && !want_xty)   // statistics only: stream the rows once, no Gram launch
-    return fold_statistics_impl<T>(X, Y, w, idx, offsets, n_folds, max_rows, K, M, flags, ddof, resolution,
-                                   gstats, out_muX, out_sdX, out_muY, out_sdY, out_fold, ws, ws_bytes, st);
-  const FoldCall c{X, Y, w, idx, offsets, N, K, M, flags, ddof, resolution, G, H, gstats,
-                   out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold, want_xty, status};
+    return small_fold_impl<T>(c, n_folds, max_rows, ws, ws_bytes, st);
+  if (!want_xtx && !c.want_xty)   // statistics only: stream the rows once, no Gram launch
+    return fold_statistics_impl<T>(c, n_folds, max_rows, ws, ws_bytes, st);
   Plan p;
   // (planned against an unlimited workspace first: the fused route below needs far less than
   //  the partials the general route plans for)
   int rc = make_plan(n_folds, max_rows, K, M, dtype, flags, (size_t)1 << 60, true, p);
-  const bool aligned = rows_aligned(X, K, sizeof(T));
-  {
-    // Folds too small to be split over workgroups (one unit per fold): finish in the Gram
-    // kernel's epilogue instead of writing partials for apply_kernel to read back.
-    WgramArgs<T> probe;
-    memset(&probe, 0, sizeof(probe));
-    probe.Y = (const T *)Y; probe.w = (const T *)w; probe.g = p.g;
-    if (p.splits == 1 && want_xtx && !sw.no_fused && wgram4_ok<T>(probe, aligned)) {
-      Geom gs = make_geom(K, M, sizeof(T), 1);
-      gs.tile_elems = 0; gs.h_elems = 0;
-      gs.unit_bytes = align_up(gs.stat_len * 8, 256);
-      const size_t fst = align_up(fstat_len(K, M) * 8, 256);
-      int64_t csplits = colstats_splits(max_rows, n_folds, K, sizeof(T), current_cu_count());
-      while (csplits > 1 && (size_t)csplits * gs.unit_bytes + fst > ws_bytes) csplits /= 2;
-      const size_t per_fold = (size_t)csplits * gs.unit_bytes + fst;
-      if (per_fold > ws_bytes) return fail(CVM_EWORKSPACE, "cvm_fold_update: workspace cannot hold one fold%s");
-      int64_t per_batch = (int64_t)(ws_bytes / per_fold);
-      if (per_batch > 16384) per_batch = 16384;
-      // Folds of up to a few hundred rows: mid_tile_kernel (mid_tile.hpp) -- small work items, four
-      // workgroups per CU, so that one item's stores overlap another's MFMAs -- behind the statistics pre-pass.
-      const bool mid = !sw.mid_off && max_rows <= mid_maxn && mid_operands_ok<T>(X, Y, w, N, K, M);
-      // Statistics formed INSIDE the Gram launch (round 4): the diagonal item of (fold, panel) sums the panel's
-      // columns while it streams the fold's rows anyway and publishes the panel's training means / stds, the
-      // off-diagonal items wait for the two flags they need (wgram4.hpp).  No colstats_kernel + fold_stats_kernel
-      // pre-pass (70-90 us in front of a 0.5-1.2 ms launch at the C3 rows cut into 100 / 1000 folds).  One Y chunk
-      // (M <= 32); CVM_FUSED_PREPASS=1: the pre-pass route (tests, comparisons).
-      // Workspace of a batch: [fstats nb x fst | flags nb x P | status 4 ints | retry list nb x off-diagonal tiles]
-      const int per0 = p.g.nTiles - p.g.P;
-      const bool ink = !mid && !sw.prepass && p.g.Yc == 1 &&
-                       fst + (size_t)p.g.P * 4 + (size_t)per0 * 8 + 512 <= per_fold;
-      for (int64_t f0 = 0; f0 < n_folds; f0 += per_batch) {
-        const int64_t nb = (n_folds - f0 < per_batch) ? n_folds - f0 : per_batch;
-        if (ink) {
-          double *fstats = (double *)ws;
-          int *sflags = (int *)((char *)ws + align_up((size_t)nb * fst, 256));
-          const size_t flag_bytes = align_up((size_t)nb * p.g.P * sizeof(int), 16);
-          int *fstatus = (int *)((char *)sflags + flag_bytes);
-          HIP_OK(hipMemsetAsync(sflags, 0, flag_bytes + 16, st));      // the flags and the two status words
-          WgramArgs<T> a = fused_args<T>(c, p, f0, nb, fstats);
-          a.stat_flags = sflags; if (!a.diag_first) a.diag_first = 1;
-          a.gstats = gstats; a.ddof = ddof; a.resolution = resolution;
-          a.out_muX = out_muX; a.out_sdX = out_sdX; a.out_muY = out_muY; a.out_sdY = out_sdY; a.out_fold = out_fold;
-          a.fused_status = fstatus;
-          a.retry_items = (unsigned long long *)((char *)fstatus + 16);
-          a.test_mode = sw.fused_test;
+  const bool aligned = rows_aligned(c.X, K, sizeof(T));
+  const bool weighted = c.w != nullptr;
+  // Folds too small to be split over workgroups (one unit per fold): finish in the Gram
+  // kernel's epilogue instead of writing partials for apply_kernel to read back.
+  if (p.splits == 1 && want_xtx && !sw.no_fused && wgram4_ok<T>(p.g.M, c.Y, c.w, aligned)) {
+    const StatPlan sp = stat_plan(K, M, esize, max_rows, n_folds, ws_bytes, 16384);
+    if (sp.per_fold > ws_bytes) return fail(CVM_EWORKSPACE, "cvm_fold_update: workspace cannot hold one fold%s");
+    // Folds of up to a few hundred rows: mid_tile_kernel (mid_tile.hpp) -- small work items, four
+    // workgroups per CU, so that one item's stores overlap another's MFMAs -- behind the statistics pre-pass.
+    const bool mid = !sw.mid_off && max_rows <= mid_maxn && mid_operands_ok<T>(c.X, c.Y, c.w, c.N, K, M);
+    // Statistics formed INSIDE the Gram launch (round 4): the diagonal item of (fold, panel) sums the panel's
+    // columns while it streams the fold's rows anyway and publishes the panel's training means / stds, the
+    // off-diagonal items wait for the two flags they need (wgram4.hpp).  No colstats_kernel + fold_stats_kernel
+    // pre-pass (70-90 us in front of a 0.5-1.2 ms launch at the C3 rows cut into 100 / 1000 folds).  One Y chunk
+    // (M <= 32); CVM_FUSED_PREPASS=1: the pre-pass route (tests, comparisons).
+    // Workspace of a batch: [fstats nb x fst | flags nb x P | status 4 ints | retry list nb x off-diagonal tiles]
+    const int per0 = p.g.nTiles - p.g.P;
+    const bool ink = !mid && !sw.prepass && p.g.Yc == 1 &&
+                     sp.fst + (size_t)p.g.P * 4 + (size_t)per0 * 8 + 512 <= sp.per_fold;
+    for (int64_t f0 = 0; f0 < n_folds; f0 += sp.per_batch) {
+      const int64_t nb = (n_folds - f0 < sp.per_batch) ? n_folds - f0 : sp.per_batch;
+      if (ink) {
+        double *fstats = (double *)ws;
+        int *sflags = (int *)((char *)ws + align_up((size_t)nb * sp.fst, 256));
+        const size_t flag_bytes = align_up((size_t)nb * p.g.P * sizeof(int), 16);
+        int *fstatus = (int *)((char *)sflags + flag_bytes);
+        HIP_OK(hipMemsetAsync(sflags, 0, flag_bytes + 16, st));      // the flags and the two status words
+        WgramArgs<T> a = fused_args<T>(c, p, f0, nb, fstats);
+        a.stat_flags = sflags; if (!a.diag_first) a.diag_first = 1;
+        a.gstats = c.gstats; a.ddof = c.ddof; a.resolution = c.resolution;
+        a.out_muX = c.out_muX; a.out_sdX = c.out_sdX; a.out_muY = c.out_muY; a.out_sdY = c.out_sdY; a.out_fold = c.out_fold;
+        a.fused_status = fstatus;
+        a.retry_items = (unsigned long long *)((char *)fstatus + 16);
+        a.test_mode = sw.fused_test;
+        {
           // (both launches between ONE pair of the timing recorder's events, like launch_mid's: the route's
           //  kernel time includes its -- normally empty, ~2 us -- retry launch)
-          TimedLaunch *tl = timed_begin(KIND_FOLD, st);
-          rc = launch_wgram<T>(a, w != nullptr, true, aligned, st, -1, wq.queue, true);
+          TimedScope timed(KIND_FOLD, st);
+          rc = launch_wgram<T>(a, weighted, true, aligned, st, -1, wq.queue, true);
           if (rc != CVM_OK) return rc;
           // the items whose wait for a flag gave up (none, unless the device is shared in a way that breaks the
           // kernel's progress argument): once more, behind the launch that has raised every flag
-          a.retry_mode = 1; a.status_out = status;
-          rc = launch_wgram<T>(a, w != nullptr, true, aligned, st, -1, wq.queue, true, 64);
-          timed_end(tl, st);
-          if (rc != CVM_OK) return rc;
-          continue;
+          a.retry_mode = 1; a.status_out = c.status;
+          rc = launch_wgram<T>(a, weighted, true, aligned, st, -1, wq.queue, true, 64);
         }
-        const double *fstats = launch_prepass<T>(c, gs, csplits, f0, nb, ws, st);
-        if (mid) rc = launch_mid<T>(mid_args(c, f0, fstats), w != nullptr, nb, max_rows, st);
-        else rc = launch_wgram<T>(fused_args<T>(c, p, f0, nb, fstats), w != nullptr, true, aligned, st, KIND_FOLD, wq.queue, true);
         if (rc != CVM_OK) return rc;
+        continue;
       }
-      return CVM_OK;
+      const double *fstats = launch_prepass<T>(c, sp, aligned, f0, nb, ws, st);
+      if (mid) rc = launch_mid<T>(mid_args(c, f0, fstats), weighted, nb, max_rows, st);
+      else rc = launch_wgram<T>(fused_args<T>(c, p, f0, nb, fstats), weighted, true, aligned, st, KIND_FOLD, wq.queue, true);
+      if (rc != CVM_OK) return rc;
     }
+    return CVM_OK;
   }
   rc = make_plan(n_folds, max_rows, K, M, dtype, flags, ws_bytes, true, p);
   if (rc != CVM_OK) return fail(rc, "cvm_fold_update: workspace cannot hold one fold%s");
   for (int64_t f0 = 0; f0 < n_folds; f0 += p.folds_per_batch) {
     const int64_t nb = (n_folds - f0 < p.folds_per_batch) ? n_folds - f0 : p.folds_per_batch;
-    char *units = (char *)ws;
-    double *fstats = (double *)((char *)ws + (size_t)nb * p.splits * p.g.unit_bytes);
-    WgramArgs<T> a;
-    memset(&a, 0, sizeof(a));
-    a.X = (const T *)X; a.Y = (const T *)Y; a.w = (const T *)w;
-    a.idx = idx; a.offs = offsets; a.N = N; a.seg0 = f0;
-    set_items(a, p, nb);
-    a.ws = units;
-    rc = launch_wgram<T>(a, w != nullptr, true, aligned, st, KIND_FOLD, wq.queue);
+    rc = launch_wgram<T>(gram_args<T>(c.X, c.Y, c.w, c.idx, c.offsets, c.N, f0, p, nb, ws), weighted, true, aligned, st,
+                         KIND_FOLD, wq.queue);
     if (rc != CVM_OK) return rc;
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.g = p.g; set_fin_splits(f, p, 1); f.n_seg = (int)nb; f.seg0 = f0; f.ws = units;
-    f.fstats = (double *)((char *)fstats);
-    f.offs = offsets; f.w = w; f.G = G; f.H = H; f.gstats = gstats;
-    f.out_XTX = (flags & CVM_RET_XTX) ? out_XTX : nullptr;
-    f.out_XTY = (flags & CVM_RET_XTY) ? out_XTY : nullptr;
-    f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
-    f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
-    hipLaunchKernelGGL((fold_stats_kernel<T>), dim3((unsigned)nb, (unsigned)fold_stats_chunks(K, M, nb)), dim3(256), 0, st, f);
-    if (f.out_XTX || f.out_XTY) {
-      f.gx = p.g.nTiles * APPLY_SUB + p.g.P; f.gy = (int)nb;
-      hipLaunchKernelGGL((apply_kernel<T, true>), dim3((unsigned)(8 * (((size_t)f.gx * f.gy + 7) / 8))),
-                         dim3(APPLY_THREADS), 0, st, f);
-    }
+    FinArgs f = fin_base(p, 1, nb, f0, ws);
+    f.fstats = (double *)((char *)ws + (size_t)nb * p.splits * p.g.unit_bytes);
+    fin_fold_side(f, c);
+    launch_fold_finalize<T>(f, nb, st);
     HIP_OK(hipGetLastError());
   }
   return CVM_OK;
@@ -1124,95 +1081,72 @@ int fold_update_impl(const void *X, const void *Y, const void *w, const int64_t 
 // sweep_fit runs the Gram kernel ONCE over all folds (gathered), sums every unit's partials
 // into G, H, gstats and leaves the partials in the workspace; sweep_folds then only runs
 // the finalize kernels on them.  Half the flops of fit + fold update.
+
+// the first half of cvm_sweep_fit and of cvm_sweep_all (`who`): the offsets' checks, the plan of all folds in one
+// batch, the Gram launch
+template <typename T>
+int sweep_gram(const char *who, const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
+               const int64_t *host_offsets, int64_t n_folds, int64_t N, int K, int M, int dtype, void *ws, size_t ws_bytes,
+               hipStream_t st, Plan &p) {
+  int64_t max_rows = 0;
+  if (int bad = fold_rows(host_offsets, n_folds, who, &max_rows, nullptr)) return bad;
+  if (!folds_cover(host_offsets, n_folds, N))
+    return fail(CVM_EINVAL, "%s: the folds must cover each of the N rows exactly once", who);
+  const WsCarve wq = carve_queue(ws, ws_bytes);
+  const int rc = make_plan(n_folds, max_rows, K, M, dtype, CVM_RET_XTX | CVM_RET_XTY, wq.usable, true, p);
+  if (rc != CVM_OK || p.folds_per_batch < n_folds)
+    return fail(CVM_EWORKSPACE, "%s: the workspace must hold the partials of all folds", who);
+  return launch_wgram<T>(gram_args<T>(X, Y, w, idx, offsets, N, 0, p, n_folds, ws), w != nullptr, true,
+                         rows_aligned(X, K, sizeof(T)), st, KIND_FOLD, wq.queue);
+}
+
 template <typename T>
 int sweep_fit_impl(const void *X, const void *Y, const void *w, const int64_t *idx,
                    const int64_t *offsets, const int64_t *host_offsets, int64_t n_folds, int64_t N,
                    int K, int M, int dtype, void *G, void *H, double *gstats, int32_t *neg_flag,
                    void *ws, size_t ws_bytes, hipStream_t st, int64_t *splits_out) {
-  int64_t max_rows = 0;
-  for (int64_t f = 0; f < n_folds; ++f) {
-    const int64_t n = host_offsets[f + 1] - host_offsets[f];
-    if (n < 0) return fail(CVM_EINVAL, "cvm_sweep_fit: offsets must be non-decreasing%s");
-    if (n > max_rows) max_rows = n;
-  }
-  if (host_offsets[n_folds] - host_offsets[0] != N)
-    return fail(CVM_EINVAL, "cvm_sweep_fit: the folds must cover each of the N rows exactly once%s");
-  const WsCarve wq = carve_queue(ws, ws_bytes);
-  ws_bytes = wq.usable;
   Plan p;
-  const unsigned flags = CVM_RET_XTX | CVM_RET_XTY;
-  int rc = make_plan(n_folds, max_rows, K, M, dtype, flags, ws_bytes, true, p);
-  if (rc != CVM_OK || p.folds_per_batch < n_folds)
-    return fail(CVM_EWORKSPACE, "cvm_sweep_fit: the workspace must hold the partials of all folds%s");
-  WgramArgs<T> a;
-  memset(&a, 0, sizeof(a));
-  a.X = (const T *)X; a.Y = (const T *)Y; a.w = (const T *)w;
-  a.idx = idx; a.offs = offsets; a.N = N; a.seg0 = 0;
-  set_items(a, p, n_folds);
-  a.ws = (char *)ws;
-  rc = launch_wgram<T>(a, w != nullptr, true, rows_aligned(X, K, sizeof(T)), st, KIND_FOLD, wq.queue);
+  const int rc = sweep_gram<T>("cvm_sweep_fit", X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, ws, ws_bytes, st, p);
   if (rc != CVM_OK) return rc;
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = p.g; set_fin_splits(f, p, (int)n_folds);      // every unit of every fold, fold-major
-  f.n_seg = 1; f.seg0 = 0; f.ws = (const char *)ws;
-  f.w = w; f.out_XTX = G; f.out_XTY = (Y && M > 0) ? H : nullptr; f.neg_flag = neg_flag;
+  FinArgs f = fin_base(p, (int)n_folds, 1, 0, ws);      // every unit of every fold, fold-major
+  fin_fit_side(f, w, G, (Y && M > 0) ? H : nullptr, neg_flag);
   // float64 with more than one row split: the fit finalize leaves every fold's raw update in the
   // fold's slot 0 (FinArgs::compact), and cvm_sweep_folds / cvm_sweep_fold_range then read one
   // partial per fold and tile (the multi-GPU step: this call, the exchange, that call -- with 1-2
   // folds per GPU the fold stage read 11-28 partials per tile: 21 us -> 6 us at C3 on 8 GPUs)
-  static const bool no_compact = getenv("CVM_NO_COMPACT") != nullptr;       // tests: the uncompacted route
-  f.compact = (sizeof(T) == 8 && !no_compact && (p.s_off > 1 || p.s_diag > 1)) ? 1 : 0;
+  f.compact = (sizeof(T) == 8 && !fold_switches().no_compact && (p.s_off > 1 || p.s_diag > 1)) ? 1 : 0;
   const bool compacted = launch_fit_apply<T>(f, p.g, gstats, st);
   HIP_OK(hipGetLastError());
-  // plan token for cvm_sweep_folds: s_off | s_diag << 20 | compacted << 40
-  if (splits_out) *splits_out = (int64_t)p.s_off | ((int64_t)p.s_diag << 20) | ((int64_t)(compacted ? 1 : 0) << 40);
+  if (splits_out) *splits_out = pack_token(p.s_off, p.s_diag, compacted);
   return CVM_OK;
 }
 
+// folds [fold0, fold0 + n_folds) of the n_total folds whose partials cvm_sweep_fit left in ws (c.offsets: of all
+// n_total folds; c.w: null); outputs are written from index 0
 template <typename T>
-int sweep_folds_impl(const int64_t *offsets, int64_t n_total, int64_t fold0, int64_t n_folds, int K, int M, int dtype,
-                     unsigned flags, double ddof, double resolution, int weighted, const void *G, const void *H,
-                     const double *gstats, void *out_XTX, void *out_XTY, void *out_muX, void *out_sdX,
-                     void *out_muY, void *out_sdY, double *out_fold, void *ws, size_t ws_bytes,
-                     int64_t splits, hipStream_t st) {
-  // folds [fold0, fold0 + n_folds) of the n_total folds whose partials cvm_sweep_fit left in ws;
-  // outputs are written from index 0
-  const Geom g = make_geom(K, M, sizeof(T), 0);
+int sweep_folds_impl(const FoldCall &c, int64_t n_total, int64_t fold0, int64_t n_folds, void *ws, size_t ws_bytes,
+                     int64_t token, hipStream_t st) {
+  const int K = c.K, M = c.M;
   Plan p;
-  p.g = g;
-  set_plan_splits(p, (int)(splits & 0xfffff), (int)((splits >> 20) & 0xfffff));
-  const bool compacted = (splits >> 40) & 1;      // every fold's slot 0 holds the sum of its partials
-  if (p.s_off < 1 || p.s_diag < 1) return fail(CVM_EINVAL, "cvm_sweep_folds: not a plan token of cvm_sweep_fit%s");
-  const size_t units = (size_t)n_total * (size_t)p.splits * g.unit_bytes;
+  p.g = make_geom(K, M, sizeof(T), 0);
+  PlanToken t;
+  if (!unpack_token(token, t)) return fail(CVM_EINVAL, "cvm_sweep_folds: not a plan token of cvm_sweep_fit%s");
+  set_plan_splits(p, t.s_off, t.s_diag);
+  const size_t units = (size_t)n_total * (size_t)p.splits * p.g.unit_bytes;
   if (units + (size_t)n_total * fstat_len(K, M) * 8 > ws_bytes)
     return fail(CVM_EWORKSPACE, "cvm_sweep_folds: workspace smaller than the one cvm_sweep_fit filled%s");
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = g; set_fin_splits(f, p, 1); f.n_seg = (int)n_folds; f.seg0 = 0;
-  if (compacted) f.s_off = f.s_diag = 1;          // (f.splits stays the slot stride)
-  f.ws = (const char *)ws + (size_t)fold0 * (size_t)p.splits * g.unit_bytes;
+  FinArgs f = fin_base(p, 1, n_folds, 0, (const char *)ws + (size_t)fold0 * (size_t)p.splits * p.g.unit_bytes);
+  if (t.compacted) f.s_off = f.s_diag = 1;        // every fold's slot 0 holds the sum of its partials (f.splits stays the slot stride)
   f.fstats = (double *)((char *)ws + units) + (size_t)fold0 * fstat_len(K, M);
-  f.offs = offsets + fold0; f.w = weighted ? (const void *)G : nullptr;   // non-null = weighted
-  f.G = G; f.H = H; f.gstats = gstats;
-  f.out_XTX = (flags & CVM_RET_XTX) ? out_XTX : nullptr;
-  f.out_XTY = (flags & CVM_RET_XTY) ? out_XTY : nullptr;
-  f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
-  f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
+  fin_fold_side(f, c);
+  f.offs = c.offsets + fold0;
   // Matrices wanted and few partials per fold (compacted: one): every workgroup of apply_kernel derives
   // the fold statistics of its tile itself and the statistics kernel is not launched at all -- one
   // launch and one launch gap less per call (the per-rank step of the multi-GPU path, the reference's
   // per-fold loop).  CVM_NO_INLINE_STATS: the two-launch route (tests).
-  static const bool no_inline = getenv("CVM_NO_INLINE_STATS") != nullptr;
   const bool mats = f.out_XTX || f.out_XTY;
-  f.inline_stats = (mats && !no_inline && f.s_diag <= 4 && M <= APPLY_INLINE_MAXM) ? 1 : 0;
-  if (!f.inline_stats)
-    hipLaunchKernelGGL((fold_stats_kernel<T>), dim3((unsigned)n_folds, (unsigned)fold_stats_chunks(K, M, n_folds)), dim3(256), 0, st, f);
-  if (mats) {
-    f.gx = g.nTiles * APPLY_SUB + g.P; f.gy = (int)n_folds;
-    hipLaunchKernelGGL((apply_kernel<T, true>), dim3((unsigned)(8 * (((size_t)f.gx * f.gy + 7) / 8))),
-                       dim3(APPLY_THREADS), 0, st, f);
-  }
+  f.inline_stats = (mats && !fold_switches().no_inline_stats && f.s_diag <= 4 && M <= APPLY_INLINE_MAXM) ? 1 : 0;
+  launch_fold_finalize<T>(f, n_folds, st);
   HIP_OK(hipGetLastError());
   return CVM_OK;
 }
@@ -1220,58 +1154,32 @@ int sweep_folds_impl(const int64_t *offsets, int64_t n_total, int64_t fold0, int
 // cvm_sweep_all: cvm_sweep_fit and cvm_sweep_folds in one call.  With few folds (<= SWF_MAX) and
 // 16-byte aligned rows the finalize half is one launch that reads every partial once
 // (sweep_finalize_kernel); otherwise the two calls' own kernels.  Same bits.
+// (c.G, c.H, c.gstats are G, H, gstats: written by the first half, read by the second)
 template <typename T>
-int sweep_all_impl(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
-                   const int64_t *host_offsets, int64_t n_folds, int64_t N, int K, int M, int dtype, unsigned flags,
-                   double ddof, double resolution, void *G, void *H, double *gstats, int32_t *neg_flag,
-                   void *out_XTX, void *out_XTY, void *out_muX, void *out_sdX, void *out_muY, void *out_sdY,
-                   double *out_fold, void *ws, size_t ws_bytes, hipStream_t st, int64_t *splits_out) {
-  static const bool no_merge = getenv("CVM_NO_SWEEP_MERGE") != nullptr;     // tests: the separate kernels
-  const bool want_xtx = flags & CVM_RET_XTX, want_xty = flags & CVM_RET_XTY;
-  const bool merged = !no_merge && n_folds <= SWF_MAX && ((size_t)K * sizeof(T)) % 16 == 0 &&
-                      ((uintptr_t)G % 16 == 0) && (!want_xtx || (uintptr_t)out_XTX % 16 == 0);
+int sweep_all_impl(const FoldCall &c, const int64_t *host_offsets, int64_t n_folds, int dtype, void *G, void *H,
+                   double *gstats, int32_t *neg_flag, void *ws, size_t ws_bytes, hipStream_t st, int64_t *splits_out) {
+  const int K = c.K, M = c.M;
+  const bool want_xtx = c.flags & CVM_RET_XTX;
+  const bool merged = !fold_switches().no_sweep_merge && n_folds <= SWF_MAX && ((size_t)K * sizeof(T)) % 16 == 0 &&
+                      ((uintptr_t)G % 16 == 0) && (!want_xtx || (uintptr_t)c.out_XTX % 16 == 0);
   if (!merged) {
     int64_t token = 0;
-    int rc = sweep_fit_impl<T>(X, Y, w, idx, offsets, host_offsets, n_folds, N, K, M, dtype, G, H, gstats, neg_flag,
-                               ws, ws_bytes, st, &token);
+    int rc = sweep_fit_impl<T>(c.X, c.Y, c.w, c.idx, c.offsets, host_offsets, n_folds, c.N, K, M, dtype, G, H, gstats,
+                               neg_flag, ws, ws_bytes, st, &token);
     if (rc != CVM_OK) return rc;
     if (splits_out) *splits_out = token;
-    return sweep_folds_impl<T>(offsets, n_folds, 0, n_folds, K, M, dtype, flags, ddof, resolution, w != nullptr, G, H,
-                               gstats, out_XTX, out_XTY, out_muX, out_sdX, out_muY, out_sdY, out_fold, ws,
-                               carve_queue(ws, ws_bytes).usable, token, st);
+    FoldCall folds = c;
+    folds.w = nullptr;                       // (as cvm_sweep_folds is called: weighted or not is all it is told)
+    return sweep_folds_impl<T>(folds, n_folds, 0, n_folds, ws, carve_queue(ws, ws_bytes).usable, token, st);
   }
-  int64_t max_rows = 0;
-  for (int64_t f = 0; f < n_folds; ++f) {
-    const int64_t n = host_offsets[f + 1] - host_offsets[f];
-    if (n < 0) return fail(CVM_EINVAL, "cvm_sweep_all: offsets must be non-decreasing%s");
-    if (n > max_rows) max_rows = n;
-  }
-  if (host_offsets[n_folds] - host_offsets[0] != N)
-    return fail(CVM_EINVAL, "cvm_sweep_all: the folds must cover each of the N rows exactly once%s");
-  const WsCarve wq = carve_queue(ws, ws_bytes);
-  ws_bytes = wq.usable;
   Plan p;
-  int rc = make_plan(n_folds, max_rows, K, M, dtype, CVM_RET_XTX | CVM_RET_XTY, ws_bytes, true, p);
-  if (rc != CVM_OK || p.folds_per_batch < n_folds)
-    return fail(CVM_EWORKSPACE, "cvm_sweep_all: the workspace must hold the partials of all folds%s");
-  WgramArgs<T> a;
-  memset(&a, 0, sizeof(a));
-  a.X = (const T *)X; a.Y = (const T *)Y; a.w = (const T *)w;
-  a.idx = idx; a.offs = offsets; a.N = N; a.seg0 = 0;
-  set_items(a, p, n_folds);
-  a.ws = (char *)ws;
-  rc = launch_wgram<T>(a, w != nullptr, true, rows_aligned(X, K, sizeof(T)), st, KIND_FOLD, wq.queue);
+  const int rc = sweep_gram<T>("cvm_sweep_all", c.X, c.Y, c.w, c.idx, c.offsets, host_offsets, n_folds, c.N, K, M, dtype, ws,
+                               ws_bytes, st, p);
   if (rc != CVM_OK) return rc;
-  const size_t units = (size_t)n_folds * (size_t)p.splits * p.g.unit_bytes;
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = p.g; set_fin_splits(f, p, 1); f.n_seg = (int)n_folds; f.seg0 = 0; f.ws = (const char *)ws;
-  f.fstats = (double *)((char *)ws + units);
-  f.offs = offsets; f.w = w; f.G = G; f.H = H; f.gstats = gstats; f.neg_flag = neg_flag;
-  f.out_XTX = want_xtx ? out_XTX : nullptr;
-  f.out_XTY = want_xty ? out_XTY : nullptr;
-  f.out_muX = out_muX; f.out_sdX = out_sdX; f.out_muY = out_muY; f.out_sdY = out_sdY;
-  f.out_fold = out_fold; f.ddof = ddof; f.resolution = resolution; f.flags = flags;
+  FinArgs f = fin_base(p, 1, n_folds, 0, ws);
+  f.fstats = (double *)((char *)ws + (size_t)n_folds * (size_t)p.splits * p.g.unit_bytes);
+  fin_fold_side(f, c);
+  f.neg_flag = neg_flag;
   // one launch, one workgroup per entry of its list (finalize.hpp): the blocks of the upper triangle that hold
   // elements, those of the diagonal tiles first, then the XTY rectangles; every workgroup forms the fold statistics
   // it needs itself.  Its LDS (the folds' updates of a block, float64) fits for every n_folds <= SWF_MAX
@@ -1288,11 +1196,11 @@ int sweep_all_impl(const void *X, const void *Y, const void *w, const int64_t *i
   constexpr int C = PPR * (16 / (int)sizeof(T));
   const unsigned xb = (unsigned)SwfList(K, C).n;
   const SwfYShape ys = swf_yshape<PPR>(M);
-  const unsigned hb = (Y && M > 0) ? (unsigned)(((K + ys.r - 1) / ys.r) * ((M + ys.w - 1) / ys.w)) : 0u;
+  const bool with_y = c.Y && M > 0;
+  const unsigned hb = with_y ? (unsigned)(((K + ys.r - 1) / ys.r) * ((M + ys.w - 1) / ys.w)) : 0u;
   hipLaunchKernelGGL((sweep_finalize_kernel<T, PPR>), dim3(xb + hb), dim3(swf4_threads<PPR>()), lds4, st, f, (T *)G,
-                     (T *)((Y && M > 0) ? H : nullptr), gstats);
+                     (T *)(with_y ? H : nullptr), gstats);
   HIP_OK(hipGetLastError());
-  if (splits_out) *splits_out = (int64_t)p.s_off | ((int64_t)p.s_diag << 20);
+  if (splits_out) *splits_out = pack_token(p.s_off, p.s_diag);
   return CVM_OK;
 }
-

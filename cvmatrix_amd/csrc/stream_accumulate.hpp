@@ -218,7 +218,7 @@ inline int stream_plan(int64_t n_folds, int64_t max_rows, int K, int M, int dtyp
 }
 
 inline size_t stream_scratch_bytes(int64_t n_folds, int64_t max_rows, int K, int M, int dtype) {
-  const int esize = dtype == CVM_F64 ? 8 : 4;
+  const int esize = esize_of(dtype);
   const Geom g = make_geom(K, M, esize, 0);
   int so = 0, sd = 0, stride = plan_stride(n_folds, max_rows, g, esize);
   const int forced = stream_forced_stride(g, so, sd);
@@ -228,26 +228,16 @@ inline size_t stream_scratch_bytes(int64_t n_folds, int64_t max_rows, int K, int
 
 template <typename T>
 int stream_add_impl(const void *X, const void *Y, const void *w, const int64_t *idx, const int64_t *offsets,
-                    const int64_t *host_offsets, int64_t n_folds, int64_t n_rows, int K, int M, int dtype, void *acc,
+                    int64_t max_rows, int64_t present, int64_t n_folds, int64_t n_rows, int K, int M, int dtype, void *acc,
                     int64_t *state, void *ws, size_t ws_bytes, hipStream_t st, int64_t *splits_out) {
-  int64_t max_rows = 0, present = 0;
-  for (int64_t f = 0; f < n_folds; ++f) {
-    const int64_t n = host_offsets[f + 1] - host_offsets[f];
-    if (n > max_rows) max_rows = n;
-    present += n > 0;
-  }
+  // (max_rows, present: the longest fold of the chunk and its folds that have rows, fold_rows)
   // the chunk's Gram launch, planned and launched as cvm_sweep_fit does
   const WsCarve wq = carve_queue(ws, ws_bytes);
   Plan p;
   if (stream_plan(n_folds, max_rows, K, M, dtype, wq.usable, p) != CVM_OK)
     return fail(CVM_EWORKSPACE, "cvm_stream_add: the workspace must hold the chunk's partials of all folds%s");
-  WgramArgs<T> a;
-  memset(&a, 0, sizeof(a));
-  a.X = (const T *)X; a.Y = (const T *)Y; a.w = (const T *)w;
-  a.idx = idx; a.offs = offsets; a.N = n_rows; a.seg0 = 0;
-  set_items(a, p, n_folds);
-  a.ws = (char *)ws;
-  int rc = launch_wgram<T>(a, w != nullptr, true, rows_aligned(X, K, sizeof(T)), st, KIND_FOLD, wq.queue);
+  int rc = launch_wgram<T>(gram_args<T>(X, Y, w, idx, offsets, n_rows, 0, p, n_folds, ws), w != nullptr, true,
+                           rows_aligned(X, K, sizeof(T)), st, KIND_FOLD, wq.queue);
   if (rc != CVM_OK) return rc;
   StreamArgs s;
   memset(&s, 0, sizeof(s));
@@ -261,7 +251,7 @@ int stream_add_impl(const void *X, const void *Y, const void *w, const int64_t *
   if (rc != CVM_OK) return rc;
   state[SS_CHUNKS] += 1; state[SS_ROWS] += n_rows; state[SS_WEIGHTED] = w != nullptr;
   if (splits_out) {
-    splits_out[0] = (int64_t)p.s_off | ((int64_t)p.s_diag << 20);
+    splits_out[0] = pack_token(p.s_off, p.s_diag);
     splits_out[1] = (int64_t)stream_add_traffic(s.gp, s.ga, p.s_off, p.s_diag, present, sizeof(T));
   }
   return CVM_OK;
@@ -284,11 +274,8 @@ int stream_close_impl(void *acc, int64_t n_folds, int K, int M, void *G, void *H
   Plan p;
   p.g = g;
   set_plan_splits(p, 1, 1);
-  FinArgs f;
-  memset(&f, 0, sizeof(f));
-  f.g = g; set_fin_splits(f, p, (int)n_folds);       // G = sum_f U_f in fold order
-  f.n_seg = 1; f.seg0 = 0; f.ws = (const char *)units;
-  f.out_XTX = G; f.out_XTY = M > 0 ? H : nullptr; f.neg_flag = neg_flag;
+  FinArgs f = fin_base(p, (int)n_folds, 1, 0, units);       // G = sum_f U_f in fold order
+  fin_fit_side(f, nullptr, G, M > 0 ? H : nullptr, neg_flag);
   launch_fit_apply<T>(f, g, gstats, st);
   HIP_OK(hipGetLastError());
   if (units_out) *units_out = units;
